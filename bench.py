@@ -17,6 +17,7 @@ import os
 import sys
 import time
 
+import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -544,15 +545,74 @@ def compact_cpu_baseline(cpu):
 DETAIL_PATH = os.path.join("gpurun_out", "bench_detail.json")
 
 
-def write_detail(detail):
-    """Per-shape / per-kernel tables, notes and sources: a file next to the run, named in the line."""
-    path = os.path.join(ROOT, DETAIL_PATH)
-    os.makedirs(os.path.dirname(path), exist_ok=True)
-    with open(path, "w") as handle:
+def detail_path():
+    """Where this run's detail document goes, as the line names it: DETAIL_PATH in the repository, or -- where the checkout is not writable --
+    a file in a fresh directory under the system's temporary directory (the benchmark writes nothing else except what --dump-outputs names)."""
+    path = os.path.join(ROOT, os.path.dirname(DETAIL_PATH))
+    try:
+        os.makedirs(path, exist_ok=True)
+        if os.access(path, os.W_OK):
+            return DETAIL_PATH
+    except OSError:
+        pass
+    import tempfile
+    return os.path.join(tempfile.mkdtemp(prefix="fb_bench_"), os.path.basename(DETAIL_PATH))
+
+
+def write_detail(detail, path=DETAIL_PATH):
+    """Per-shape / per-kernel tables, notes and sources: a file next to the run, named in the line (``path``: relative to the repository, or absolute)."""
+    with open(os.path.join(ROOT, path), "w") as handle:
         json.dump(detail, handle, indent=1)
 
 
-def assemble_line(base, extra, roof=None, side=None, cpu=None):
+DUMP_SAMPLE = 1 << 22       # --dump-outputs: an array of more elements is written as this many of them (16 MiB in float32) ...
+DUMP_SEED = 20240229        # ... at indices drawn once from this seed: the same elements on every run and every build
+DUMP_MAX_BYTES = 64 << 20
+
+
+def last_step_outputs(trainer):
+    """What the timed path hands its caller after its last step, as host arrays: the parameters (``model.parameters()`` order, the model's own
+    layouts, concatenated), the averaged gradient and the momentum of that step in the same order, the BatchNorm running statistics
+    (``model.named_buffers()`` order) and the step's statistics record."""
+    eng, stats = trainer.engine, trainer.stats
+
+    def flat(arena):
+        return torch.cat([t.reshape(-1) for t in eng.unflatten_list(arena.detach().float().cpu())]).numpy()
+
+    layer_of_bn = {L.bn_name: L for L in eng.plan.layers}
+    bns = [layer_of_bn[n[:-len(".running_mean")]] for n, _ in trainer.model.named_buffers() if n.endswith(".running_mean")]
+    rm, rv = eng.running_mean.float().cpu(), eng.running_var.float().cpu()
+    keys = ("train_loss", "train_acc", "grad_norm", "param_norm", "full_loss")
+    return {"params": flat(eng.theta), "grad": flat(eng.avg), "momentum": flat(eng.mom),
+            "bn_running_mean": torch.cat([rm[L.ch_off:L.ch_off + L.cout] for L in bns]).numpy(),
+            "bn_running_var": torch.cat([rv[L.ch_off:L.ch_off + L.cout] for L in bns]).numpy(),
+            "chunk_grad_norms": np.array([stats[f"grad_norm_train_{k}"][-1] for k in range(trainer.n_chunks)], dtype=np.float64),
+            "step_stats": np.array([stats[k][-1] for k in keys], dtype=np.float64)}          # in the order of `keys`
+
+
+def write_outputs(out_dir, arrays):
+    """``{name: float32 / float64 array}`` -> ``out_dir/<name>.npy``, flattened; arrays of more than DUMP_SAMPLE elements are replaced by the
+    elements at DUMP_SAMPLE sorted indices drawn from DUMP_SEED (the same indices for every array of one length).  Returns the bytes written."""
+    picks, out = {}, {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a).reshape(-1)
+        if a.dtype not in (np.float32, np.float64):
+            raise TypeError(f"--dump-outputs: {name} is {a.dtype}, not float32 / float64")
+        if a.size > DUMP_SAMPLE:
+            if a.size not in picks:
+                picks[a.size] = np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, DUMP_SAMPLE, replace=False))
+            a = a[picks[a.size]]
+        out[name] = a
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes > {DUMP_MAX_BYTES}")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    return total
+
+
+def assemble_line(base, extra, roof=None, side=None, cpu=None, detail_file=DETAIL_PATH):
     """(the ONE JSON line rank 0 prints, the detail document).  ``roof`` = roofline_objects(), ``side`` = side_configs(), ``cpu`` =
     cpu_baseline().  The driver parses the last stdout line out of a bounded tail: a line above MAX_LINE_BYTES is an error here, not there."""
     out, detail = dict(base), dict(base, **extra)
@@ -567,10 +627,10 @@ def assemble_line(base, extra, roof=None, side=None, cpu=None):
     if cpu is not None:
         detail["cpu_baseline"] = cpu
         out["cpu_baseline"] = compact_cpu_baseline(cpu)
-    out["detail"] = DETAIL_PATH
+    out["detail"] = detail_file
     line = json.dumps(out, separators=(",", ":"))
     if len(line) > MAX_LINE_BYTES:
-        raise RuntimeError(f"bench line is {len(line)} bytes (> {MAX_LINE_BYTES}); move fields to {DETAIL_PATH}")
+        raise RuntimeError(f"bench line is {len(line)} bytes (> {MAX_LINE_BYTES}); move fields to {detail_file}")
     return line, detail
 
 
@@ -623,7 +683,12 @@ def main():
     ap.add_argument("--serialize", action="store_true",
                     help="run the weight-gradient kernels on the main stream and take the per-kernel HIP-event timings inside the "
                          "timed region (the protocol the rocprofv3 summaries under profiles/ are generated with)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed (parameters, averaged gradient, momentum, BN running "
+                         "statistics, step statistics) as DIR/<name>.npy, float32 / float64, at most 64 MiB (seeded samples of large arrays)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.r152_child:
         torch.cuda.set_device(0)
@@ -687,8 +752,8 @@ def main():
     headline = (args.model, args.stem, args.pixels) == ("resnet18", "CIFAR", 32)
     if not headline:
         overrides += [f"model={args.model}", f"model.stem={args.stem}", f"data.pixels={args.pixels}"]
+    # (original_cwd: where train() would keep checkpoints; the benchmark writes nothing there, and the directory need not exist or be writable)
     cfg = compose(overrides, original_cwd=os.path.join(ROOT, "gpurun_out"), name="bench")
-    os.makedirs(cfg.original_cwd, exist_ok=True)
 
     # synthetic CIFAR-shaped data, generated identically on every rank
     gen = torch.Generator().manual_seed(1234)
@@ -729,6 +794,11 @@ def main():
         rank_ms = [round(1000 * float(e[0]) / args.steps, 2) for e in every]
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
     elapsed = float(t[0])
+    # ---- --dump-outputs: the state the last timed step left, read back after the clock stopped and before anything else steps ----
+    if args.dump_outputs:
+        trainer.gather_state()       # (collective, a no-op on one rank: the whole momentum / gradient arenas after sharded updates)
+        if rank == 0:
+            write_outputs(args.dump_outputs, last_step_outputs(trainer))
     # ---- outside the step: the stem's im2col patch gather of the static dataset (once, before the timed region) -- timed here on its own ----
     outside_ms = None
     if trainer.patches is not None and trainer.augment is None and trainer.shuffler is None:
@@ -840,8 +910,9 @@ def main():
                     print(f"bench.py: the ResNet-152 configurations failed: {exc}", file=sys.stderr)
         if world == 1 and not args.no_cpu_baseline:
             cpu = cpu_baseline()
-        line, detail = assemble_line(out, extra, roof, side, cpu)
-        write_detail(detail)
+        where = detail_path()
+        line, detail = assemble_line(out, extra, roof, side, cpu, detail_file=where)
+        write_detail(detail, where)
         sys.stdout.flush()
         print(line, flush=True)
     if world > 1 or force_dist:

@@ -566,14 +566,67 @@ def test_bench_line_reports_a_failed_resnet152_child_inside_the_line():
     assert json.loads(line)["configs"]["r152_error"]["steps"] == 0
 
 
-def test_power_sampler_without_a_gpu_reports_nothing(tmp_path):
-    """bench.PowerSampler reads the amdgpu hwmon files of the process's GPU from a host thread; where there is no such device (this container) or the
+def test_bench_dump_writer_samples_large_arrays_at_fixed_indices(tmp_path):
+    """`bench.py --dump-outputs DIR` writes float32 / float64 arrays, at most 64 MiB in all: an array above DUMP_SAMPLE elements becomes the same seeded
+    sample on every call (so that the dumps of two builds compare element for element), smaller ones are written whole, other dtypes are refused."""
+    import bench
+
+    rng = np.random.default_rng(0)
+    big = rng.standard_normal(bench.DUMP_SAMPLE + 12345).astype(np.float32)
+    arrays = {"params": big, "grad": -big, "stats": np.arange(5, dtype=np.float64)}
+    total = bench.write_outputs(str(tmp_path / "a"), arrays)
+    bench.write_outputs(str(tmp_path / "b"), arrays)
+    got = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in arrays}
+    assert total == sum(a.nbytes for a in got.values()) <= bench.DUMP_MAX_BYTES
+    assert got["params"].dtype == np.float32 and got["params"].shape == (bench.DUMP_SAMPLE,)
+    assert np.array_equal(got["grad"], -got["params"])                        # one index set for arrays of one length
+    assert np.isin(got["params"], big).all() and np.array_equal(got["stats"], arrays["stats"])
+    for n in arrays:
+        assert np.array_equal(got[n], np.load(tmp_path / "b" / f"{n}.npy"))
+    with pytest.raises(TypeError):
+        bench.write_outputs(str(tmp_path / "c"), {"labels": np.arange(3)})
+    with pytest.raises(RuntimeError, match="bytes >"):
+        bench.write_outputs(str(tmp_path / "d"), {f"a{i}": big for i in range(5)})
+
+
+def test_bench_detail_document_leaves_a_read_only_checkout_alone(tmp_path, monkeypatch):
+    """bench.py runs from checkouts it may not write to: the detail document then goes to a fresh temporary directory and the line names that file;
+    where the directory of DETAIL_PATH can be made or written, it stays DETAIL_PATH.  (Unwritable here: a FILE of that name, which blocks the directory
+    for any user.)"""
+    import json
+    import tempfile
+
+    import bench
+
+    out_dir = os.path.dirname(bench.DETAIL_PATH)
+    (tmp_path / "tmp").mkdir()
+    monkeypatch.setattr(tempfile, "tempdir", str(tmp_path / "tmp"))               # (the fallback's directory lands inside this test's own)
+    monkeypatch.setattr(bench, "ROOT", str(tmp_path / "writable"))
+    assert bench.detail_path() == bench.DETAIL_PATH and (tmp_path / "writable" / out_dir).is_dir()
+    blocked = tmp_path / "blocked"
+    blocked.mkdir()
+    (blocked / out_dir).write_text("")
+    monkeypatch.setattr(bench, "ROOT", str(blocked))
+    where = bench.detail_path()
+    assert os.path.isabs(where) and where.startswith(str(tmp_path / "tmp")) and os.path.isdir(os.path.dirname(where))
+    base = {"metric": "m", "value": 1.0, "unit": "images/s", "ms_per_step": 2.0}
+    line, detail = bench.assemble_line(base, {"note": "n"}, detail_file=where)
+    bench.write_detail(detail, where)
+    assert json.loads(line)["detail"] == where and json.load(open(where))["note"] == "n"
+    assert sorted(os.listdir(blocked)) == [out_dir]                       # nothing written into the checkout
+
+
+def test_power_sampler_without_a_gpu_reports_nothing(tmp_path, monkeypatch):
+    """bench.PowerSampler reads the amdgpu hwmon files of the process's GPU from a host thread; where there is no such device or the
     files are unreadable it must stay out of the way: start() is a no-op and result() is None (the line then carries ``"power": null``).  With a
     directory that looks like hwmon it samples, averages and converts the units (microwatts -> W, Hz -> MHz)."""
     import time
 
     import bench
 
+    def no_device(index):
+        raise RuntimeError("no HIP device")           # what the device query does on a host without a GPU -- here on every host, GPU or not
+    monkeypatch.setattr(torch.cuda, "get_device_properties", no_device)
     ps = bench.PowerSampler(0)
     assert ps.dir is None
     ps.start()

@@ -321,11 +321,16 @@ def test_bench_two_ranks_spawn_and_tear_down_on_one_gpu(tmp_path):
     import subprocess
     import sys
     env = dict(os.environ, FB_BENCH_SHARE_DEVICE="1")
-    res = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--images", "2048", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"],
-                         env=env, capture_output=True, text=True, timeout=200)
+    res = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--images", "2048", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+                          "--dump-outputs", str(tmp_path / "dump")], env=env, capture_output=True, text=True, timeout=200)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
     out = json.loads(lines[0])
     assert out["n_gpus"] == 2 and out["steps"] == 2 and out["value"] > 0 and np.isfinite(out["train_loss_last"])
     assert out["config"]["parallelism"].startswith("dp2") and "roofline" in out
+    # --dump-outputs on two ranks: rank 0 writes the whole state (momentum and gradient gathered from the shards) of the last timed step
+    dump = {f[:-4]: np.load(tmp_path / "dump" / f) for f in os.listdir(tmp_path / "dump")}
+    assert {"params", "grad", "momentum", "chunk_grad_norms", "step_stats"} <= set(dump) and dump["chunk_grad_norms"].size == 2048 // 128
+    assert all(np.isfinite(v).all() for v in dump.values()) and dump["step_stats"][0] == out["train_loss_last"]
+    assert (dump["momentum"] != 0).mean() > 0.9          # both ranks' shards, not rank 0's alone (the rest would still be zero)

@@ -391,3 +391,38 @@ def test_train_from_lmdb_record_database(golden, tmp_path):
     for key in ("train_loss", "grad_norm", "param_norm", "full_loss", "preclip_gradnorm", "train_acc"):
         assert np.allclose(stats[key], want[key], rtol=2e-3, atol=1.01 / 46 if key == "train_acc" else 1e-6), (key, stats[key], want[key])
     assert abs(stats["train_loss"][0] - want["train_loss"][0]) < 1e-5 * want["train_loss"][0]
+
+
+def test_bench_dump_outputs_repeat_exactly(tmp_path):
+    """`bench.py --dump-outputs DIR` writes what the timed path computed in its last timed step.  Two runs with the same arguments start from the
+    same seeded data and initialisation and take every reduction in a fixed order, so their dumps agree bit for bit; the arrays are float32 /
+    float64, within 64 MiB, and sized by the model and the chunk count; the loss among them is the one the JSON line reports."""
+    import json
+    import subprocess
+    import sys
+
+    import bench
+    from fullbatchtraining_amd.cfg import compose
+    from fullbatchtraining_amd.models import construct_model
+
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dumps, lines = [], []
+    for run in ("a", "b"):
+        res = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--images", "2048", "--steps", "2", "--warmup", "1",
+                              "--no-cpu-baseline", "--no-side-configs", "--no-kernel-timing", "--dump-outputs", str(tmp_path / run)],
+                             capture_output=True, text=True, timeout=200)
+        assert res.returncode == 0, res.stderr[-2000:]
+        lines.append(json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1]))
+        dumps.append({f[:-4]: np.load(tmp_path / run / f) for f in sorted(os.listdir(tmp_path / run))})
+    out, (a, b) = lines[0], dumps
+    assert out["steps"] == 2 and out["ms_per_step"] > 0
+    model = construct_model(compose([]).model, 3, 10)
+    n_params = sum(p.numel() for p in model.parameters())
+    n_bn = sum(t.numel() for n, t in model.named_buffers() if n.endswith(".running_mean"))
+    assert set(a) == {"params", "grad", "momentum", "bn_running_mean", "bn_running_var", "chunk_grad_norms", "step_stats"}
+    assert a["params"].size == min(n_params, bench.DUMP_SAMPLE) and a["bn_running_var"].size == n_bn and a["chunk_grad_norms"].size == 2048 // 128
+    assert sum(v.nbytes for v in a.values()) <= bench.DUMP_MAX_BYTES
+    for name in a:
+        assert a[name].dtype in (np.float32, np.float64) and np.isfinite(a[name]).all(), name
+        assert np.array_equal(a[name], b[name]), name
+    assert a["step_stats"][0] == out["train_loss_last"] and np.abs(a["grad"]).max() > 0

@@ -18,6 +18,7 @@ from oracle import fb_oracle as orc
 from tests.helpers import NOISE_SEED, hyp_from_cfg, loader_pass_indices, make_data, rel_err, shuffling_loaders, summarise
 
 F64 = torch.float64
+GOLDEN_THREADS = 8          # torch CPU threads of the run that wrote tests/golden (make_golden.py)
 
 
 def _setup(meta, name, dtype=torch.float32):
@@ -38,7 +39,14 @@ def _key(name, dtype):
 def test_init_matches_reference_bitwise(golden, name):
     data, meta = golden
     _, model, _, _, _ = _setup(meta, name)
-    per, samp = summarise([v.float() for v in model.state_dict().values()])
+    # the per-tensor float64 sums of the golden file come from torch's multi-threaded CPU reduction with 8 threads, and the order of that
+    # reduction follows the thread count (1, 2, 4, 16 or 32 threads move them by 1-2 ulp): summed here with the same 8, whatever the host has
+    saved = torch.get_num_threads()
+    torch.set_num_threads(GOLDEN_THREADS)
+    try:
+        per, samp = summarise([v.float() for v in model.state_dict().values()])
+    finally:
+        torch.set_num_threads(saved)
     assert np.array_equal(samp.astype(np.float32), data[f"{name}/init_sample"].astype(np.float32))
     assert np.array_equal(per, data[f"{name}/init_per"])
 
