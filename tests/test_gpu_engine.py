@@ -858,3 +858,78 @@ def test_chunk_chained_weight_gradients_opt_in(monkeypatch):
     L = eng.chain_layers[0]
     sl = slice(L.w_off, L.w_off + L.cout * L.taps * L.cin_real)
     assert float((a0[sl] - a1[sl]).norm() / a0[sl].norm()) < 2e-6
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32], ids=["bf16", "fp32-bf16x6"])
+def test_resnet18_production_chunk_group_vs_oracle(dtype, monkeypatch):
+    """The headline's chunk group end to end: ONE group of 98 distinct chunks of 128 images (default dispatch, replayed command list) against the float64
+    oracle's chunk gradient on sampled chunks (0, 1, the last, two seeded others) -- fp32: 3e-3 relative L2 (the reference's own fp32 noise), cosine 0.99999,
+    loss 1e-5; bf16: the torch-autocast yardstick of test_resnet18_chunk_gradients_vs_oracle.  Then full_gradient over 390 chunks (groups of 98/98/98/96: the
+    last one short of the nominal group): the step's mean gradient and every chunk's squared norm against float64 reductions of the engine's own per-chunk
+    gradients, collected group by group (the engine is bit-deterministic)."""
+    import os
+    import random
+
+    from tests.helpers import err_cos, flat64, torch_bf16_chunk_grads
+
+    for k in list(os.environ):                   # the default dispatch
+        if k.startswith("FB_") and k not in ("FB_EXPERIMENTAL", "FB_ORACLE_DEVICE", "FB_TEST_TIMEOUT_S", "FB_TEST_WATCHDOG_S", "FB_SOAK"):
+            monkeypatch.delenv(k)
+    pixels, chunk, G, n_chunks = 32, 128, 98, 390
+    cfg, model, eng, stem_patches = _build(18, pixels, chunk, G, dtype)
+    assert eng.use_replay
+    x, y = make_data(chunk * n_chunks, pixels, seed=4321)
+    patches, yd = stem_patches(x.cuda(), eng.plan.stem, dtype), y.cuda()
+    eng.prep_weights(eng.theta, 1)
+    runs = []
+    for _ in range(2):                           # recorded, then replayed: the same bits
+        eng.group_gradient(patches[:G * chunk], yd[:G * chunk], G, eng.g)
+        torch.cuda.synchronize()
+        runs.append((eng.g[:G].clone(), eng.loss[:G].clone(), eng.correct[:G].clone()))
+    assert eng.replays >= 1 and all(torch.equal(a, b) for a, b in zip(*runs))
+    smp = sorted({0, 1, G - 1} | set(random.Random(0).sample(range(2, G - 1), 2)))
+    xs = torch.cat([x[g * chunk:(g + 1) * chunk] for g in smp])
+    ys = torch.cat([y[g * chunk:(g + 1) * chunk] for g in smp])
+    truth, _, _ = _oracle_chunk_grads(model, xs, ys, chunk)
+    got = _engine_grads_as_lists(eng, G)
+    if dtype == torch.bfloat16:
+        ref, _, _ = _oracle_chunk_grads(model, xs, ys, chunk, emulate_bf16=True)
+        yard = torch_bf16_chunk_grads(model, xs, ys, chunk, device="cuda")
+    for i, g in enumerate(smp):
+        a, t = flat64(got[g]), flat64(truth[i][0])
+        e_eng, c_eng = err_cos(a, t)
+        if dtype == torch.float32:
+            print(f"[fp32, group of {G}] chunk {g}: engine-vs-f64 {e_eng:.3e}, cosine {c_eng:.7f}, loss {float(eng.loss[g]):.6f} vs {truth[i][1]:.6f}")
+            assert e_eng < 3e-3 and c_eng > 0.99999, (g, e_eng, c_eng)
+            assert abs(float(eng.loss[g]) - truth[i][1]) < 1e-5 * max(1.0, abs(truth[i][1])), g
+            assert float(eng.correct[g]) == truth[i][2], g
+        else:
+            e_tch, c_tch = err_cos(flat64(yard[i][0]), t)
+            print(f"[bf16, group of {G}] chunk {g}: engine {e_eng:.3f} / cos {c_eng:.4f}; torch autocast(bf16) {e_tch:.3f} / cos {c_tch:.4f}")
+            assert e_eng <= 1.15 * e_tch and c_eng >= c_tch - 0.01, (g, e_eng, e_tch, c_eng, c_tch)
+            assert abs(float(eng.loss[g]) - ref[i][1]) < 2e-3 * max(1.0, abs(ref[i][1])), g
+            assert abs(float(eng.loss[g]) - yard[i][1]) < 2e-2 * max(1.0, abs(yard[i][1])), g
+    # the whole step: 390 chunks in groups of 98/98/98/96
+    loss, correct, sq = eng.full_gradient(patches, yd, 0.1)
+    torch.cuda.synchronize()
+    avg, sq = eng.avg.double().clone(), sq.double().clone()
+    total = torch.zeros(eng.plan.P, dtype=torch.float64, device="cuda")
+    sq64 = torch.zeros(n_chunks, dtype=torch.float64, device="cuda")
+    sizes = []
+    for lo in range(0, n_chunks, G):
+        g_n = min(G, n_chunks - lo)
+        sizes.append(g_n)
+        eng.prep_weights(eng.theta, 1)
+        eng.group_gradient(patches[lo * chunk:(lo + g_n) * chunk], yd[lo * chunk:(lo + g_n) * chunk], g_n, eng.g)
+        torch.cuda.synchronize()
+        assert torch.equal(eng.loss[:g_n], loss[lo:lo + g_n])
+        for g in range(g_n):
+            row = eng.g[g].double()
+            total += row
+            sq64[lo + g] = row.pow(2).sum()
+    assert sizes == [98, 98, 98, 96]
+    mean64 = total / n_chunks
+    e_mean = float((avg - mean64).norm() / mean64.norm())
+    e_sq = float(((sq - sq64).abs() / sq64).max())
+    print(f"[{dtype}] full_gradient over {n_chunks} chunks: mean gradient vs float64 {e_mean:.2e}, chunk squared norms (worst) {e_sq:.2e}")
+    assert e_mean < 1e-5 and e_sq < 1e-5
