@@ -207,3 +207,186 @@ def to_oracle(*tensors, dtype=torch.float64):
     dev = oracle_device()
     out = tuple(t.to(dev, dtype) if t.is_floating_point() else t.to(dev) for t in tensors)
     return out[0] if len(out) == 1 else out
+
+
+# ----------------------------------------------------------------------------------------------------------------------------------
+# float64 references of the update / regulariser kernels (csrc/multi_tensor.hip) with ELEMENTWISE error bounds that follow from the
+# arithmetic: u = 2^-24 (one fp32 rounding, relative) times the sum of the absolute values of the terms of the expression times the
+# number of roundings on the longest path.  Shared by tests/test_cpu_bounds.py (fp32 torch emulations of the kernels + planted errors:
+# the checker is shown to bite) and tests/test_gpu_update_production.py (the kernels at arena size).  Every function works on tensors of
+# any device, one row at a time, and takes the host-side scalars ROUNDED TO fp32 (`f32r`): they reach the kernels as `float`, and the
+# scalar's own rounding (0.9f vs 0.9: 2.6e-8 relative) is larger than the bounds.
+U32 = 2.0 ** -24
+COEF_ROUNDINGS = 4       # clip / (sqrtf(norm2) + 1e-6f), eps / sqrtf(vnorm2): sqrt, add, divide + one of slack, relative
+
+
+def f32r(x):
+    """The value a Python float has once it is passed to a kernel as ``float``."""
+    return float(np.float32(x))
+
+
+def within_bound(got, ref, bound):
+    """(worst |got - ref| / bound, flat index of it).  ``ref`` float64, ``bound`` a float64 tensor (or a number) >= 0; where the bound is 0
+    the values must be equal (ratio 0 if they are, inf otherwise); a NaN anywhere counts as inf."""
+    if got.numel() == 0:
+        return 0.0, -1
+    err = (got.double() - ref).abs().reshape(-1)
+    b = torch.as_tensor(bound, dtype=torch.float64, device=err.device).expand(got.shape).reshape(-1)
+    ratio = torch.where(err == 0, torch.zeros_like(err), err / b)
+    ratio = torch.nan_to_num(ratio, nan=float("inf"), posinf=float("inf"))
+    i = int(torch.argmax(ratio))
+    return float(ratio[i]), i
+
+
+def running_mean_ref(a0, rows, counter0):
+    """The running mean a_{j+1} = a_j + (v_j - a_j) / (c + j + 1) of fb_mt_accumulate (and of the mean inside fb_mt_fd_combine_accumulate) as a
+    float64 recurrence, with the bound B carried alongside: B += u * (3 |v_j - a_j| / (c+j+1) + |a_{j+1}|) per folded chunk (the subtraction, the
+    product and the fp32 rounding of 1/(c+j+1); the sum).  An earlier error is multiplied by 1 - 1/(c+j+1) <= 1, so the terms add up.
+    ``rows`` yields v_j, or (v_j, e_j) where e_j bounds the error v_j itself arrives with (the recombined gradient): B += e_j / (c+j+1).
+    -> (mean, B, sum of the v_j), all float64."""
+    a = a0.double().clone()
+    B, total = torch.zeros_like(a), torch.zeros_like(a)
+    for j, v in enumerate(rows):
+        v, e = v if isinstance(v, tuple) else (v, None)
+        v = v.double()
+        inv = 1.0 / (counter0 + j + 1)
+        total += v
+        d = v - a
+        a += d * inv
+        B += d.abs_() * (3 * U32 * inv)
+        B += a.abs() * U32
+        if e is not None:
+            B += e * inv
+    return a, B, total
+
+
+def reduction_bound(count, blocks, r, extra=0.0):
+    """Relative error of a two-stage sum of non-negative terms: fp32 partials per thread (``r`` roundings per iteration, ``count`` iterations
+    spread over ``blocks`` workgroups of 256 threads), a 16-deep fp32 tree inside the workgroup, the second stage in double."""
+    iters = -(-int(count) // (int(blocks) * 256))
+    return (r * iters + 16) * U32 + extra
+
+
+def clip_coef_ref(norm2, clip):
+    """(coef, hit) of the clip the kernels form from the device scalar ``norm2`` (an fp32 value): norm > clip -> clip / (norm + 1e-6).  The
+    kernels form it in fp32: COEF_ROUNDINGS * u relative is allowed wherever it enters."""
+    if clip is None or clip < 0:
+        return 1.0, False
+    norm, c = float(np.sqrt(np.float64(np.float32(norm2)))), f32r(clip)
+    if not norm > c:
+        return 1.0, False
+    return c / (norm + f32r(1e-6)), True
+
+
+def sgd_ref(p, g, m, coef, hit, lr, weight_decay, momentum, dampening, nesterov, first):
+    """fb_mt_clip_sgd in float64 -> {"grad" | "mom" | "param": (reference, bound)}.  With S = |coef g| + wd |p| + mu |m|:
+    clipped gradient u |coef g| (+ the allowance on coef; not clipped: the bits of g), momentum 4u S, parameters u (|p| + |p'| + 8 lr S);
+    where the clip is hit the allowance on coef (COEF_ROUNDINGS u |coef g|) passes linearly into the momentum (factor <= 1) and the
+    parameters (factor <= lr (1 + mu))."""
+    lr, wd, mu, damp = f32r(lr), f32r(weight_decay), f32r(momentum), f32r(dampening)
+    p, g = p.double(), g.double()
+    cg = g * coef
+    ce = COEF_ROUNDINGS * U32 * cg.abs() if hit else torch.zeros_like(cg)
+    d = cg + wd * p
+    S = cg.abs() + wd * p.abs()
+    out = {"grad": (cg, U32 * cg.abs() + ce if hit else torch.zeros_like(cg))}
+    if mu != 0.0:
+        if first:
+            buf = d
+        else:
+            buf = mu * m.double() + (1.0 - damp) * d
+            S = S + mu * m.double().abs()
+        out["mom"] = (buf, 4 * U32 * S + ce)
+        d = d + mu * buf if nesterov else buf
+    pn = p - lr * d
+    out["param"] = (pn, U32 * (p.abs() + pn.abs() + 8 * lr * S) + lr * (1 + mu) * ce)
+    return out
+
+
+def fd_combine_ref(g, ga, gb, eps_j, cf):
+    """gt = g + cf (ga - gb) / eps_j (fb_mt_fd_combine, and per chunk inside fb_mt_fd_combine_accumulate): (gt, u (3 cf |ga - gb| / eps_j + |gt|)) --
+    the difference, the quotient and the product are amplified by cf / eps_j, the sum is not.  ``eps_j``: the fp32 value the kernel reads."""
+    cf = f32r(cf)
+    amp = (ga.double() - gb.double()) * (cf / float(eps_j))
+    gt = g.double() + amp
+    return gt, U32 * (3 * amp.abs_() + gt.abs())
+
+
+def fd_perturb_ref(theta0, g, s, alpha, pre=None, acc=0.0):
+    """theta0 + alpha (s g + acc pre) of fb_mt_fd_perturb (alpha = sign * eps_n[j] in float64):
+    (out, u (|theta0| + 3 |alpha| (|s g| + |acc pre|) + |out|))."""
+    s, acc = f32r(s), f32r(acc)
+    w = s * g.double()
+    mag = w.abs()
+    if pre is not None:
+        q = acc * pre.double()
+        w = w + q
+        mag = mag + q.abs()
+    out = theta0.double() + alpha * w
+    return out, U32 * (theta0.double().abs() + 3 * abs(alpha) * mag + out.abs())
+
+
+def accumulate_sum_ref(a, gsum, counter0, n_groups):
+    """fb_mt_accumulate_sum: a + (gsum - G a) / (c + G): (out, u (4 (|gsum| + G |a|) / (c + G) + |out|)) -- G a, the difference, the product with
+    the fp32-rounded 1/(c+G) and that rounding; the sum."""
+    a, gsum = a.double(), gsum.double()
+    inv = 1.0 / (counter0 + n_groups)
+    out = a + (gsum - n_groups * a) * inv
+    return out, U32 * (4 * (gsum.abs() + n_groups * a.abs()) * inv + out.abs())
+
+
+def scale_ref(x, a):
+    """fb_mt_scale / the clip-free product: ONE correctly rounded fp32 product: (a x, u |a x|)."""
+    out = f32r(a) * x.double()
+    return out, U32 * out.abs()
+
+
+def sam_ref(theta, g, norm2, clip, rho):
+    """fb_mt_sam_ascent as the reference states it (sam.py:56-69 after the closure's clip): g_c = coef g, e = g_c rho / (|g_c| + 1e-12) with
+    |g_c| the float64 norm OF THE CLIPPED VECTOR (the kernel forms it as sqrt(norm2) * coef), theta' = theta + e.
+    -> {"e": ..., "theta": ...}.  e: the two products, sqrt, product, add, divide of the scale, one for norm2's own fp32 rounding: 7u |e|, and
+    twice the allowance on coef where the clip is hit; theta': that + u |theta'|."""
+    coef, hit = clip_coef_ref(norm2, clip)
+    gc = g.double() * coef
+    norm_c = float(gc.pow(2).sum().sqrt())
+    e = gc * (f32r(rho) / (norm_c + f32r(1e-12)))
+    be = (7 + (2 * COEF_ROUNDINGS if hit else 0)) * U32 * e.abs()
+    tn = theta.double() + e
+    return {"e": (e, be), "theta": (tn, be + U32 * tn.abs()), "norm_c": norm_c, "coef": coef, "hit": hit}
+
+
+def norm_bias_ref(grad, theta, pnorm2, strength, bias, norm_type):
+    """fb_mt_norm_bias: diff = pnorm2 - bias^2; type 1: grad + strength sign(diff) (one rounding); else grad + 2 strength diff theta, where
+    c = 2 strength diff carries u (2 |2 strength| (pnorm2 + bias^2) + |c|) (bias^2, the difference; the product) and the update one rounding
+    for c theta and one for the sum."""
+    strength, bias, pn2 = f32r(strength), f32r(bias), float(np.float32(pnorm2))
+    diff = pn2 - bias * bias
+    g, t = grad.double(), theta.double()
+    if norm_type == 1:
+        out = g + strength * (1.0 if diff > 0 else (-1.0 if diff < 0 else 0.0))
+        return out, U32 * out.abs()
+    c = strength * 2.0 * diff
+    c_err = U32 * (2 * abs(2 * strength) * (pn2 + bias * bias) + abs(c))
+    out = g + c * t
+    return out, c_err * t.abs() + U32 * ((c * t).abs() + out.abs())
+
+
+SENTINEL = 1.2345e30     # fills the padding columns between a row's n values and the group stride: no kernel may touch them
+
+
+def distinct_rows(G, n, stride, scale, seed, device, bands=True):
+    """[G, stride] fp32 test rows: seeded randn * scale; a band of 1000 columns scaled by 1e3 and another by 1e-3; row j multiplied by 1 + j/G
+    (a row mix-up changes every result); the padding columns [n, stride) hold SENTINEL."""
+    gen = torch.Generator(device=device).manual_seed(seed)
+    buf = torch.empty(G, stride, device=device, dtype=torch.float32)
+    buf.normal_(generator=gen).mul_(scale)
+    if bands and n > 8000:
+        buf[:, 5000:6000] *= 1e3
+        buf[:, n // 2:n // 2 + 1000] *= 1e-3
+    buf *= (1.0 + torch.arange(G, device=device, dtype=torch.float32) / G)[:, None]
+    buf[:, n:] = SENTINEL
+    return buf
+
+
+def padding_untouched(buf, n):
+    return bool((buf[..., n:] == SENTINEL).all())

@@ -1,0 +1,280 @@
+"""The float64 references and arithmetic bounds of tests/helpers.py (used at arena size by tests/test_gpu_update_production.py) are shown to
+bite, on the CPU: fp32 torch emulations of the kernels of csrc/multi_tensor.hip (the same operations in the same order, one rounding each) pass
+them, and every planted error below fails them:
+  * one element off by twice its own bound at the last index (per kernel: the bound of a 98-chunk mean is ~100 u |a|, of a momentum 4 u S);
+  * the scalar tail (the last n % 4 elements) left unprocessed;
+  * rows j and j+1 swapped (per-row norms, per-row eps_n of the recombination: the plain mean is symmetric in its rows and cannot see it);
+  * 1/(c+j) instead of 1/(c+j+1);
+  * one grid-stride pass skipped (elements [grid*256, 2*grid*256) untouched);
+and the scalar rule: a float64 reference with the unrounded 0.9 fails an honest fp32 momentum update, with float32(0.9) it passes.
+1 M elements (n % 4 == 2), 98 chunks, counters 0 and 292, the magnitude bands of the GPU cases."""
+import numpy as np
+import pytest
+import torch
+
+from tests.helpers import (U32, accumulate_sum_ref, clip_coef_ref, distinct_rows, f32r, fd_combine_ref, fd_perturb_ref, norm_bias_ref, reduction_bound,
+                           running_mean_ref, sam_ref, sgd_ref, within_bound)
+
+N, G = 1_000_002, 98
+GRID = 1024                     # emulated launch: GRID workgroups of 256 threads -> four grid-stride passes over N
+F = torch.float32
+
+
+def _f(x):
+    return torch.tensor(x, dtype=F)
+
+
+def _mean_f32(a0, rows, c0, inv_of=lambda c0, j: 1.0 / (c0 + j + 1)):
+    """mt_accumulate_kernel in fp32 torch: a += (v - a) * (float)(1.0 / (double)(c0 + j + 1))."""
+    a = a0.clone()
+    for j, v in enumerate(rows):
+        a = a + (v - a) * _f(inv_of(c0, j))
+    return a
+
+
+@pytest.fixture(scope="module")
+def rows():
+    torch.manual_seed(0)
+    return distinct_rows(G, N, N, 1e-2, 11, "cpu")
+
+
+@pytest.fixture(scope="module")
+def a0():
+    return torch.randn(N, generator=torch.Generator().manual_seed(5)) * 1e-2
+
+
+@pytest.fixture(scope="module", params=[0, 292])
+def mean_case(request, rows, a0):
+    c0 = request.param
+    ref, B, total = running_mean_ref(a0, rows, c0)
+    return c0, _mean_f32(a0, rows, c0), ref, B, total
+
+
+def test_within_bound_reports_the_worst_element():
+    ref = torch.zeros(5, dtype=torch.float64)
+    got = torch.tensor([0.0, 1.0, -3.0, 0.5, 0.0])
+    assert within_bound(got, ref, torch.full((5,), 2.0, dtype=torch.float64)) == (1.5, 2)
+    assert within_bound(got, ref, 4.0) == (0.75, 2)
+    assert within_bound(torch.zeros(3), torch.zeros(3, dtype=torch.float64), 0.0) == (0.0, 0)               # bound 0: equality
+    assert within_bound(torch.tensor([0.0, 1e-30]), torch.zeros(2, dtype=torch.float64), 0.0) == (float("inf"), 1)
+    assert within_bound(torch.tensor([0.0, float("nan")]), torch.zeros(2, dtype=torch.float64), 1.0) == (float("inf"), 1)
+    assert within_bound(torch.zeros(0), torch.zeros(0, dtype=torch.float64), 1.0) == (0.0, -1)
+
+
+def test_reduction_bound_values():
+    # ResNet-18's arena: 11 float4 per thread in the float4 kernels, 43 elements per thread in the scalar ones -- both inside the 1e-5 the project uses
+    assert reduction_bound(11_173_962 // 4, 1024, 8) == (8 * 11 + 16) * U32 < 1e-5
+    assert reduction_bound(11_173_962, 1024, 2) == (2 * 43 + 16) * U32 < 1e-5
+    assert reduction_bound(60_192_808, 1024, 2) == (2 * 230 + 16) * U32
+    assert reduction_bound(10, 1024, 2, extra=4 * U32) == 22 * U32
+
+
+def test_running_mean_honest_fp32_passes_and_recurrence_equals_closed_form(mean_case, a0):
+    c0, got, ref, B, total = mean_case
+    closed = (c0 * a0.double() + total) / (c0 + G)
+    assert float((ref - closed).abs().max()) <= 1e-13 * max(1.0, float(closed.abs().max()))
+    ratio, i = within_bound(got, ref, B)
+    print(f"running mean, c0={c0}: honest fp32 worst error/bound {ratio:.3f} at {i}; B/(u|a|) median {float((B / (U32 * ref.abs())).median()):.0f}")
+    assert ratio <= 1.0
+
+
+def test_running_mean_planted_errors_fail(mean_case, rows, a0):
+    c0, got, ref, B, _ = mean_case
+    bad = got.clone()                                     # one element, twice its own bound, at the last index
+    bad[-1] = (ref[-1] + 2.0 * B[-1]).float()
+    assert abs(float(bad[-1]) - float(ref[-1])) > float(B[-1])
+    ratio, i = within_bound(bad, ref, B)
+    assert ratio > 1.0 and i == N - 1
+    bad = got.clone()                                     # the scalar tail left unprocessed
+    bad[N - N % 4:] = a0[N - N % 4:]
+    ratio, i = within_bound(bad, ref, B)
+    assert ratio > 1.0 and i >= N - N % 4
+    bad = got.clone()                                     # the second grid-stride pass skipped
+    bad[GRID * 256:2 * GRID * 256] = a0[GRID * 256:2 * GRID * 256]
+    ratio, i = within_bound(bad, ref, B)
+    assert ratio > 1.0 and GRID * 256 <= i < 2 * GRID * 256
+    if c0:                                                # 1/(c+j) instead of 1/(c+j+1)
+        ratio, _ = within_bound(_mean_f32(a0, rows, c0, lambda c, j: 1.0 / (c + j)), ref, B)
+        assert ratio > 1.0
+    # a fixed 16u |a| would NOT do as the bound of a 98-chunk mean: the honest result exceeds it
+    assert within_bound(got, ref, 16 * U32 * ref.abs())[0] > 1.0
+
+
+def test_row_norms_see_swapped_rows(rows):
+    """The mean is symmetric in its rows; the per-row outputs (fused squared norms) are not: the reduction bound tells rows j, j+1 apart."""
+    sq64 = rows.double().pow(2).sum(1)
+    sq32 = (rows * rows).sum(1)                           # an honest fp32 reduction (torch's pairwise order)
+    bound = reduction_bound(N // 4, min(-(-(N // 4) // 256), 1024), 8)
+    assert float(((sq32.double() - sq64).abs() / sq64).max()) <= bound
+    swapped = sq32.clone()
+    swapped[[40, 41]] = sq32[[41, 40]]
+    assert float(((swapped.double() - sq64).abs() / sq64).max()) > 1e-5 > bound
+
+
+@pytest.mark.parametrize("c0", [0, 292])
+def test_fd_recombination_bound_and_planted_errors(rows, a0, c0):
+    """vhp = (ga - gb) / eps_n[j]; gt = g + cf vhp; running mean -- mt_fd_combine_kernel in fp32 torch."""
+    cf = 0.1 / 4
+    eps = torch.linspace(1e-3, 1.1e-2, G, dtype=F)
+    gen = torch.Generator().manual_seed(3)
+    ga = rows + 1e-4 * torch.randn(G, N, generator=gen)
+
+    def kernel(eps_rows, first_only=False):
+        a, gts = a0.clone(), []
+        for j in range(G):
+            vhp = (ga[j] - rows[j]) / eps_rows[j]
+            gt = rows[j] + _f(cf) * vhp
+            if first_only:
+                gts.append(gt)
+            a = a + (gt - a) * _f(1.0 / (c0 + j + 1))
+            if first_only and j == 1:
+                break
+        return a, gts
+
+    def refs():
+        for j in range(G):
+            yield fd_combine_ref(rows[j], ga[j], rows[j], float(eps[j]), cf)
+
+    ref, B, _ = running_mean_ref(a0, refs(), c0)
+    got, _ = kernel(eps)
+    ratio, i = within_bound(got, ref, B)
+    print(f"fd recombination + mean, c0={c0}: honest fp32 worst error/bound {ratio:.3f} at {i}")
+    assert ratio <= 1.0
+    # per element (fb_mt_fd_combine): honest passes, twice the bound at the last index fails
+    _, gts = kernel(eps, first_only=True)
+    gt_ref, gt_b = fd_combine_ref(rows[1], ga[1], rows[1], float(eps[1]), cf)
+    assert within_bound(gts[1], gt_ref, gt_b)[0] <= 1.0
+    bad = gts[1].clone()
+    bad[-1] = (gt_ref[-1] + 2.0 * gt_b[-1]).float()
+    assert within_bound(bad, gt_ref, gt_b) == (pytest.approx(2.0, rel=0.3), N - 1)
+    # eps_n of rows 40 and 41 swapped: the recombination is not symmetric in its rows
+    sw = eps.clone()
+    sw[[40, 41]] = eps[[41, 40]]
+    assert within_bound(kernel(sw)[0], ref, B)[0] > 1.0
+    # the fused mean, one element off by twice its own bound at the last index
+    bad = got.clone()
+    bad[-1] = (ref[-1] + 2.0 * B[-1]).float()
+    assert within_bound(bad, ref, B)[0] > 1.0
+
+
+def _sgd_f32(p, g, m, coef, lr, wd, mu, damp, nesterov, first):
+    """mt_clip_sgd_kernel in fp32 torch."""
+    gr = g * _f(coef) if coef != 1.0 else g
+    d = gr + _f(wd) * p
+    buf = None
+    if mu != 0.0:
+        buf = d if first else _f(mu) * m + (_f(1.0) - _f(damp)) * d
+        d = d + _f(mu) * buf if nesterov else buf
+    return gr, buf, p - _f(lr) * d
+
+
+@pytest.fixture(scope="module")
+def sgd_inputs(rows):
+    gen = torch.Generator().manual_seed(9)
+    p = distinct_rows(1, N, N, 1.0, 21, "cpu")[0]
+    m = distinct_rows(1, N, N, 1e-2, 22, "cpu")[0]
+    return p, rows[3].clone(), m, gen
+
+
+@pytest.mark.parametrize("first,nesterov,damp,mu,clip", [(1, 1, 0.0, 0.9, None), (0, 1, 0.0, 0.9, None), (0, 0, 0.1, 0.9, None), (0, 1, 0.1, 0.9, "hit"),
+                                                          (0, 1, 0.0, 0.9, "miss"), (0, 1, 0.0, 0.0, "hit")])
+def test_sgd_bounds_and_planted_errors(sgd_inputs, first, nesterov, damp, mu, clip):
+    p, g, m, _ = sgd_inputs
+    lr, wd = 0.1, 5e-4
+    norm2 = float(np.float32(float(g.double().pow(2).sum())))
+    norm = norm2 ** 0.5
+    clipv = None if clip is None else (0.5 * norm if clip == "hit" else 2.0 * norm)
+    coef, hit = clip_coef_ref(norm2, clipv)
+    assert hit == (clip == "hit")
+    coef32 = float(_f(clipv) / (_f(norm2).sqrt() + _f(1e-6))) if hit else 1.0
+    gr, buf, pn = _sgd_f32(p, g, m, coef32, lr, wd, mu, damp, nesterov, first)
+    ref = sgd_ref(p, g, m if mu else None, coef, hit, lr, wd, mu, damp, nesterov, first)
+    got = {"grad": gr, "param": pn, **({"mom": buf} if mu else {})}
+    assert set(got) == set(ref)
+    for k in got:
+        ratio, i = within_bound(got[k], *ref[k])
+        print(f"sgd first={first} nesterov={nesterov} damp={damp} mu={mu} clip={clip}: {k} worst error/bound {ratio:.3f}")
+        assert ratio <= 1.0, (k, ratio, i)
+    for k in ("param",) + (("mom",) if mu else ()):
+        r, b = ref[k]
+        bad = got[k].clone()
+        bad[-1] = (r[-1] + 2.0 * b[-1]).float()
+        ratio, i = within_bound(bad, r, b)
+        assert ratio > 1.0 and i == N - 1, k
+        bad = got[k].clone()                               # the second grid-stride pass skipped
+        src = p if k == "param" else m
+        bad[GRID * 256:2 * GRID * 256] = src[GRID * 256:2 * GRID * 256]
+        assert within_bound(bad, r, b)[0] > 1.0, k
+
+
+def test_scalar_rule_references_use_fp32_rounded_scalars(sgd_inputs):
+    """Host scalars reach the kernels as float: the reference must use float32(0.9), not 0.9 (2.6e-8 = 0.44 u relative).
+    Where a bound is one rounding wide the unrounded scalar alone breaks it: x * 0.9f (fb_mt_scale, bound u |a x|: a single correctly
+    rounded product) FAILS against 0.9 x and passes against float32(0.9) x.  For the momentum update the unrounded reference is measurably
+    worse, but it cannot leave the bound 4 u S by itself: every scalar is within u of its fp32 value, so the reference moves by at most u S = a quarter
+    of the bound (measured here: 0.20; the worst error/bound goes from 0.49 to 0.61) -- that case asserts the shift, not a failure."""
+    import tests.helpers as H
+
+    p, g, m, _ = sgd_inputs
+    got = g * _f(0.9)
+    assert within_bound(got, *H.scale_ref(g, 0.9))[0] <= 1.0
+    ratio = within_bound(got, 0.9 * g.double(), U32 * (0.9 * g.double()).abs())[0]
+    print(f"x * 0.9f vs a float64 reference with the unrounded 0.9: worst error/bound {ratio:.2f}")
+    assert ratio > 1.0
+    assert f32r(0.9) != 0.9 and abs(f32r(0.9) - 0.9) / 0.9 > 2e-8
+    _, buf, pn = _sgd_f32(p, g, m, 1.0, 0.1, 5e-4, 0.9, 0.0, 1, 0)
+    good = sgd_ref(p, g, m, 1.0, False, 0.1, 5e-4, 0.9, 0.0, 1, 0)
+    r_good = within_bound(buf, *good["mom"])[0]
+    assert r_good <= 1.0 and within_bound(pn, *good["param"])[0] <= 1.0
+    keep = H.f32r
+    H.f32r = float                                        # the same reference with the scalars left in double precision
+    try:
+        bad = H.sgd_ref(p, g, m, 1.0, False, 0.1, 5e-4, 0.9, 0.0, 1, 0)
+    finally:
+        H.f32r = keep
+    r_bad = within_bound(buf, *bad["mom"])[0]
+    shift = float(((bad["mom"][0] - good["mom"][0]).abs() / good["mom"][1]).max())
+    print(f"momentum: worst error/bound {r_good:.2f} with float32 scalars, {r_bad:.2f} with unrounded ones (reference moved by up to {shift:.2f} of the bound)")
+    assert r_bad > r_good and 0.05 < shift <= 0.25
+
+
+def test_remaining_elementwise_references_accept_honest_fp32(sgd_inputs, rows):
+    p, g, m, _ = sgd_inputs
+    # fb_mt_fd_perturb
+    s, acc, eps = 0.5, 0.3, 1e-2
+    v2 = float(np.float32(float((f32r(s) * g.double() + f32r(acc) * m.double()).pow(2).sum())))
+    eps_n32 = _f(eps) / _f(v2).sqrt()
+    eps_n64 = f32r(eps) / v2 ** 0.5
+    assert abs(float(eps_n32) - eps_n64) <= 4 * U32 * eps_n64
+    alpha = _f(-0.5) * eps_n32
+    out = p + alpha * (_f(s) * g + _f(acc) * m)
+    assert within_bound(out, *fd_perturb_ref(p, g, s, -0.5 * eps_n64, m, acc))[0] <= 1.0
+    bad = out.clone()
+    bad[N - N % 4:] = p[N - N % 4:]
+    assert within_bound(bad, *fd_perturb_ref(p, g, s, -0.5 * eps_n64, m, acc))[0] > 1.0
+    # fb_mt_accumulate_sum
+    gsum = rows.double().sum(0).float()
+    a = m
+    got = a + (gsum - _f(float(G)) * a) * _f(1.0 / (292 + G))
+    r, b = accumulate_sum_ref(a, gsum, 292, G)
+    assert within_bound(got, r, b)[0] <= 1.0
+    assert within_bound(a + (gsum - _f(float(G)) * a) * _f(1.0 / (291 + G)), r, b)[0] > 1.0
+    # fb_mt_sam_ascent (clip hit and not)
+    norm2 = float(np.float32(float(g.double().pow(2).sum())))
+    for clip in (None, 0.5 * norm2 ** 0.5):
+        ref = sam_ref(p, g, norm2, clip, 0.05)
+        norm = _f(norm2).sqrt()
+        coef = _f(clip) / (norm + _f(1e-6)) if clip is not None else _f(1.0)
+        e = (g * coef) * (_f(0.05) / (norm * coef + _f(1e-12)))
+        assert ref["hit"] == (clip is not None)
+        assert abs(float(norm * coef) - ref["norm_c"]) <= (2 + 4) * U32 * ref["norm_c"]
+        assert within_bound(e, *ref["e"])[0] <= 1.0 and within_bound(p + e, *ref["theta"])[0] <= 1.0
+        assert within_bound(e * _f(1.0 + 2e-6), *ref["e"])[0] > 1.0
+    # fb_mt_norm_bias
+    pn2 = float(np.float32(float(p.double().pow(2).sum())))
+    for nt, bias in ((1, 0.9 * pn2 ** 0.5), (1, 1.1 * pn2 ** 0.5), (2, 0.9 * pn2 ** 0.5)):
+        diff = _f(pn2) - _f(bias) * _f(bias)
+        got = g + (_f(0.01) * torch.sign(diff) if nt == 1 else (_f(0.01) * (_f(2.0) * diff)) * p)
+        r, b = norm_bias_ref(g, p, pn2, 0.01, bias, nt)
+        assert within_bound(got, r, b)[0] <= 1.0, (nt, bias)
+        assert within_bound(g - (got - g), r, b)[0] > 1.0, (nt, bias)              # the wrong sign
