@@ -390,3 +390,104 @@ def distinct_rows(G, n, stride, scale, seed, device, bands=True):
 
 def padding_untouched(buf, n):
     return bool((buf[..., n:] == SENTINEL).all())
+
+
+# ----------------------------------------------------------------------------------------------------------------------------------
+# BatchNorm running statistics and evaluation coefficients (csrc/bn.hip bn_running_update_kernel, csrc/head_pool.hip bn_eval_coeffs_kernel)
+# as float64 references with elementwise bounds from the arithmetic.  Shared by tests/test_cpu_bounds.py (fp32 emulations + planted errors),
+# tests/test_gpu_running_stats.py and tests/test_gpu_eval.py.
+BN_EPS = 1e-5
+BN_MOMENTUM = 0.1
+
+
+def bessel(valid_images, hout, wout):
+    """m / (m - 1) with m = real images of a BN batch x pixels of the feature map, as the fp32 value the kernel multiplies by."""
+    m = int(valid_images) * int(hout) * int(wout)
+    return f32r(m / (m - 1))
+
+
+def bn_running_ref(rm0, rv0, updates, momentum=BN_MOMENTUM):
+    """Running mean / variance after ``updates`` = [(batch mean row, BIASED batch variance row, Bessel factor: number or per-channel tensor)]
+    applied in that order: r <- keep r + mom x with keep = fl(1 - fl(mom)) (the kernel forms it in fp32; the scalars through ``f32r``), x the
+    mean, or the variance times the Bessel factor.  -> (mean, var, bound_mean, bound_var), float64.  Bound per update: three roundings (the two
+    products, the sum): B <- keep B + u (|keep r| + |mom x| + |r'|); the variance one more for var * ub: + u |mom x|.  An earlier error is
+    multiplied by keep < 1, so the terms add up."""
+    mom = f32r(momentum)
+    keep = float(np.float32(1.0) - np.float32(momentum))
+    m, v = rm0.double().clone(), rv0.double().clone()
+    Bm, Bv = torch.zeros_like(m), torch.zeros_like(v)
+    for mean, var, ub in updates:
+        ub = ub.double().to(m.device) if torch.is_tensor(ub) else float(ub)
+        xm, xv = mom * mean.double().to(m.device), mom * (var.double().to(m.device) * ub)
+        m_new, v_new = keep * m + xm, keep * v + xv
+        Bm = keep * Bm + U32 * ((keep * m).abs() + xm.abs() + m_new.abs())
+        Bv = keep * Bv + U32 * ((keep * v).abs() + 2 * xv.abs() + v_new.abs())
+        m, v = m_new, v_new
+    return m, v, Bm, Bv
+
+
+def bn_eval_coeffs_ref(gamma, beta, rm, rv, eps=BN_EPS):
+    """scale = gamma / sqrt(rv + eps), shift = beta - rm scale (BatchNorm2d in eval mode) -> (scale, shift, bound_scale, bound_shift), float64.
+    The kernel: the sum rv + eps, sqrtf, the reciprocal, the product: 4u |scale|; the shift: the product rm * scale (carrying scale's error)
+    and the difference: u (5 |rm scale| + |shift|)."""
+    g, b, m, v = gamma.double(), beta.double(), rm.double(), rv.double()
+    scale = g / (v + f32r(eps)).sqrt()
+    shift = b - m * scale
+    return scale, shift, 4 * U32 * scale.abs(), U32 * (5 * (m * scale).abs() + shift.abs())
+
+
+def mean_loss_bound(n, classes, logits64, labels):
+    """Bound on |fp32 mean cross entropy - float64 mean cross entropy| of the SAME logits (fb_head_loss: a thread per image, then one sequential
+    fp32 sum over the n images and a division; in the style of ``reduction_bound``): per image l = lse - (z_t - max), with z - max (one rounding),
+    ``classes`` exponentials (2 ulp each) and their sequential sum (relative (classes + 2) u of a sum in [1, classes]), logf (2 ulp), the
+    difference: u (2 |z_t - max| + (classes + 2) + 3 lse + l); the sum of n non-negative terms: (n - 1) u relative, the division one more."""
+    z = logits64.double()
+    zm = z - z.max(dim=1, keepdim=True).values
+    lse = zm.exp().sum(dim=1).log()
+    zt = zm[torch.arange(z.shape[0], device=z.device), labels]
+    li = lse - zt
+    per_image = U32 * (2 * zt.abs() + (classes + 2) + 3 * lse + li)
+    return float(per_image.mean() + n * U32 * li.mean())
+
+
+def eval_state(model, spec, x, seed=11, stat_images=32):
+    """Parameters and running statistics under which evaluation is NOT degenerate (at the init state gamma = 1, beta = 0, running statistics
+    (0, 1) make every BatchNorm the identity), written into ``model`` (the parameter container) in place:
+      * gamma ~ U(0.5, 1.5), beta ~ N(0, 0.1) in every BatchNorm;
+      * running mean / (unbiased) variance = the float64 oracle's train-mode batch statistics of ``x[:stat_images]``;
+      * in every layer two channels on the epsilon path: ``running_var`` exactly 0 in one and exactly 1e-6 in the other.  So that these
+        channels leave their BatchNorm with O(1) values -- gamma / sqrt(eps) = 316 gamma on an O(1) channel in each of 20 .. 53 layers compounds
+        to an overflow -- the rows of the convolution weight that produce them are scaled by 1e-4 and 1e-3 first: the channels' true variance is
+        then ~1e-8 and ~1e-6, the recorded one 0 and 1e-6, and eps decides the result (without it: inf, and a factor 3.3).
+    -> {bn name: (channel with running_var 0, channel with running_var 1e-6)}."""
+    from oracle import fb_oracle as orc
+
+    gen = torch.Generator().manual_seed(seed)
+    sd = model.state_dict()
+    names = spec.bn_names()
+    conv_of = {bn: (bn[:-1] + "0" if bn == "stem.1" else (bn.replace(".downsample.2", ".downsample.1") if "downsample" in bn else bn.replace(".bn", ".conv")))
+               for bn in names}
+    eps_ch = {}
+    with torch.no_grad():
+        for li, bn in enumerate(names):
+            C = sd[f"{bn}.weight"].numel()
+            sd[f"{bn}.weight"].copy_(0.5 + torch.rand(C, generator=gen))
+            sd[f"{bn}.bias"].copy_(0.1 * torch.randn(C, generator=gen))
+            c0, c1 = 1 + li % 5, C - 2 - li % 3
+            eps_ch[bn] = (c0, c1)
+            w = sd[f"{conv_of[bn]}.weight"]
+            w[c0] *= 1e-4
+            w[c1] *= 1e-3
+        state = {k: (v.detach().clone().double() if v.is_floating_point() else v.detach().clone()).to(oracle_device()) for k, v in sd.items()}
+        params, buffers = orc.split_state(state)
+        for bn in names:                      # (running statistics (0, 0) + one update with momentum 0.1: the buffers hold 0.1 x the batch statistics)
+            buffers[f"{bn}.running_mean"].zero_()
+            buffers[f"{bn}.running_var"].zero_()
+        orc.forward(spec, params, buffers, to_oracle(x[:stat_images]), update_bn=True, train=True)
+        for bn in names:
+            c0, c1 = eps_ch[bn]
+            rv = (buffers[f"{bn}.running_var"] / orc.BN_MOMENTUM).float().cpu()
+            rv[c0], rv[c1] = 0.0, 1e-6
+            sd[f"{bn}.running_mean"].copy_((buffers[f"{bn}.running_mean"] / orc.BN_MOMENTUM).float().cpu())
+            sd[f"{bn}.running_var"].copy_(rv)
+    return eps_ch

@@ -278,3 +278,126 @@ def test_remaining_elementwise_references_accept_honest_fp32(sgd_inputs, rows):
         r, b = norm_bias_ref(g, p, pn2, 0.01, bias, nt)
         assert within_bound(got, r, b)[0] <= 1.0, (nt, bias)
         assert within_bound(g - (got - g), r, b)[0] > 1.0, (nt, bias)              # the wrong sign
+
+
+# ----------------------------------------------------------------------------------------------------------------------------------
+# BatchNorm running statistics (helpers.bn_running_ref, used by tests/test_gpu_running_stats.py) and the evaluation coefficients (helpers.
+# bn_eval_coeffs_ref + the walk's tensor bounds, used by tests/test_gpu_eval.py): an fp32 torch emulation of bn_running_update_kernel /
+# bn_eval_coeffs_kernel passes, every planted error fails.
+RS_CH, RS_CHUNKS, RS_CHUNK, RS_VALID, RS_HW = 200, 5, 32, 30, 16
+
+
+def _running_f32(rm0, rv0, mean_tab, var_tab, unbias, n_chunks, n_passes, order="chunk-major", momentum=0.1, drop=None, biased=False, decay_new=False):
+    """bn_running_update_kernel in fp32 torch: for g: for p: m = keep m + mom mean[p, g]; v = keep v + mom (var[p, g] ub).  The switches plant the errors."""
+    mom = _f(momentum)
+    keep = _f(1.0) - mom
+    m, v = rm0.clone(), rv0.clone()
+    steps = [(p, g) for g in range(n_chunks) for p in range(n_passes)] if order == "chunk-major" else [(p, g) for p in range(n_passes) for g in range(n_chunks)]
+    for i, (p, g) in enumerate(steps):
+        if drop == i:
+            continue
+        var = var_tab[p, g] if biased else var_tab[p, g] * unbias
+        if decay_new:                                    # momentum applied to the OLD value: r = mom r + keep x
+            m, v = mom * m + keep * mean_tab[p, g], mom * v + keep * var
+        else:
+            m, v = keep * m + mom * mean_tab[p, g], keep * v + mom * var
+    return m, v
+
+
+@pytest.fixture(scope="module")
+def running_case():
+    from tests.helpers import bessel, bn_running_ref
+    gen = torch.Generator().manual_seed(3)
+    rm0, rv0 = torch.randn(RS_CH, generator=gen), 0.5 + torch.rand(RS_CH, generator=gen)
+    mean_tab = torch.randn(3, RS_CHUNKS, RS_CH, generator=gen) * 0.5
+    var_tab = 0.2 + torch.rand(3, RS_CHUNKS, RS_CH, generator=gen)
+    ub = bessel(RS_VALID, 4, 4)
+    unbias = torch.full((RS_CH,), ub, dtype=F)
+    refs = {}
+    for n_passes in (1, 2, 3):
+        ups = [(mean_tab[p, g], var_tab[p, g], ub) for g in range(RS_CHUNKS) for p in range(n_passes)]
+        refs[n_passes] = bn_running_ref(rm0, rv0, ups)
+    return rm0, rv0, mean_tab, var_tab, unbias, refs
+
+
+@pytest.mark.parametrize("n_passes", [1, 2, 3])
+def test_bn_running_ref_honest_fp32_passes(running_case, n_passes):
+    rm0, rv0, mean_tab, var_tab, unbias, refs = running_case
+    m, v = _running_f32(rm0, rv0, mean_tab, var_tab, unbias, RS_CHUNKS, n_passes)
+    rm, rv, Bm, Bv = refs[n_passes]
+    a, b = within_bound(m, rm, Bm)[0], within_bound(v, rv, Bv)[0]
+    print(f"running statistics, {n_passes} pass(es): honest fp32 worst error/bound mean {a:.3f}, var {b:.3f}; bound / (u |r|) median "
+          f"{float((Bm / (U32 * rm.abs())).median()):.1f} / {float((Bv / (U32 * rv.abs())).median()):.1f}")
+    assert a <= 1.0 and b <= 1.0
+    # the decay of the start value is visible: (1 - m)^K of it is still there
+    K = RS_CHUNKS * n_passes
+    assert float((rm - (0.9 ** K) * rm0.double()).abs().max()) > 1e-3 and 0.9 ** K > 0.2
+
+
+def test_bn_running_ref_planted_errors_fail(running_case):
+    from tests.helpers import bessel
+    rm0, rv0, mean_tab, var_tab, unbias, refs = running_case
+
+    def ratios(n_passes, **kw):
+        m, v = _running_f32(rm0, rv0, mean_tab, var_tab, kw.pop("unbias", unbias), RS_CHUNKS, n_passes, **kw)
+        rm, rv, Bm, Bv = refs[n_passes]
+        return within_bound(m, rm, Bm)[0], within_bound(v, rv, Bv)[0]
+
+    a, b = ratios(1, biased=True)                         # biased instead of unbiased variance: the mean cannot see it, the variance must
+    assert a <= 1.0 and b > 1.0
+    # the Bessel factor of the STORED chunk (32 images) instead of the real one (30): 1/511 against 1/479, 1.3e-4 relative
+    a, b = ratios(1, unbias=torch.full((RS_CH,), bessel(RS_CHUNK, 4, 4), dtype=F))
+    assert a <= 1.0 and b > 1.0
+    assert all(r > 1.0 for r in ratios(2, order="pass-major"))      # pass-major instead of chunk-major order
+    assert all(r <= 1.0 for r in ratios(1, order="pass-major"))     # (one pass: the two orders are the same)
+    assert all(r > 1.0 for r in ratios(2, drop=0))                  # one update dropped: the oldest one, whose weight 0.9^9 is the smallest
+    assert all(r > 1.0 for r in ratios(3, drop=14))
+    assert all(r > 1.0 for r in ratios(1, decay_new=True))          # momentum 0.1 applied to the old value instead of the new
+
+
+def _eval_bn_f32(x_nhwc, gamma, beta, rm, rv, eps, with_eps=True):
+    """bn_eval_coeffs_kernel + the apply pass (y = max(x scale + shift, 0)) in fp32 torch"""
+    sc = gamma * (_f(1.0) / torch.sqrt(rv + _f(eps) if with_eps else rv))
+    sh = beta - rm * sc
+    return sc, sh, torch.relu(x_nhwc * sc + sh)
+
+
+@pytest.mark.parametrize("bf16", [False, True], ids=["fp32", "bf16"])
+def test_eval_coefficient_without_eps_fails_the_walk_bounds(bf16):
+    """The evaluation walk's tensor bounds (tests/test_gpu_bf16_structural._Checks: REL_L2 / REL_L2_F32, 2 ulp on all but BAD_FRACTION) and the
+    coefficient bound of helpers.bn_eval_coeffs_ref: an honest fp32 emulation passes both, rsqrt(var) without eps fails both -- on the two
+    epsilon-path channels (running_var 0: inf; 1e-6: a factor 3.3), two of 64."""
+    from oracle import fb_oracle as orc
+    from tests.helpers import BN_EPS, bn_eval_coeffs_ref
+    from tests.test_gpu_bf16_structural import _Checks
+
+    gen = torch.Generator().manual_seed(9)
+    C, c0, c1 = 64, 3, 61
+    x = torch.randn(6, C, 8, 8, generator=gen, dtype=torch.float64)
+    x[:, c0] *= 1e-4
+    x[:, c1] *= 1e-3
+    q = (lambda t: t.to(torch.bfloat16).to(t.dtype)) if bf16 else (lambda t: t.to(F).to(t.dtype))
+    x = q(x)
+    gamma, beta = (0.5 + torch.rand(C, generator=gen)).double(), (0.1 * torch.randn(C, generator=gen)).double()
+    rm, rv = x.mean((0, 2, 3)).float().double(), x.var((0, 2, 3)).float().double()
+    rv[c0], rv[c1] = 0.0, float(np.float32(1e-6))
+    buffers = {"bn.running_mean": rm, "bn.running_var": rv}
+    ref = q(torch.relu(orc.bn_eval_fwd(x, gamma, beta, buffers, "bn")))
+    sc64, sh64, bsc, bsh = bn_eval_coeffs_ref(gamma, beta, rm, rv, BN_EPS)
+    for with_eps in (True, False):
+        sc, sh, y = _eval_bn_f32(x.permute(0, 2, 3, 1).float(), gamma.float(), beta.float(), rm.float(), rv.float(), BN_EPS, with_eps)
+        ck = _Checks(fp32=not bf16)
+        ck.close(y.to(torch.bfloat16) if bf16 else y, ref, "BN + ReLU, eval coefficients")
+        coef = max(within_bound(sc, sc64, bsc)[0], within_bound(sh, sh64, bsh)[0])
+        print(f"{'bf16' if bf16 else 'fp32'}, eps {'kept' if with_eps else 'dropped'}: {ck.report[0]}, coefficients error/bound {coef:.3g}")
+        if with_eps:
+            honest = y
+            assert not ck.fails and coef <= 1.0
+        else:
+            assert ck.fails and coef > 1.0
+            assert bool(((sc.double() - sc64).abs() > bsc)[[c0, c1]].all())
+            if bf16:                                     # (the other channels are 5e-6 off: below a bf16 ulp, only the coefficient bound sees them)
+                y[..., [c0, c1]] = honest[..., [c0, c1]]
+                ck = _Checks(fp32=False)
+                ck.close(y.to(torch.bfloat16), ref, "BN + ReLU, eps dropped on the ordinary channels only")
+                assert not ck.fails
