@@ -56,8 +56,11 @@ class ConvBN:
 
 
 class Block:
-    def __init__(self, convs, shortcut, stride, cin, hin, win):
-        self.convs, self.shortcut, self.stride, self.cin, self.hin, self.win = convs, shortcut, stride, cin, hin, win
+    """``kind``: the shortcut's form -- None (identity), 'C' (AvgPool2d(stride) -> 1x1 conv -> BN) or 'B' (1x1 conv with the block's stride -> BN,
+    executed as a spatial subsample followed by the same 1x1 stride-1 convolution)."""
+
+    def __init__(self, convs, shortcut, stride, cin, hin, win, kind=None):
+        self.convs, self.shortcut, self.stride, self.cin, self.hin, self.win, self.kind = convs, shortcut, stride, cin, hin, win, kind
 
 
 def max_group(plan, chunk, dtype, device=None, reserve_bytes=0, use_free=True, fd_sets=0):
@@ -156,11 +159,20 @@ class Plan:
                     c2 = ConvBN(f"{p}.conv2", f"{p}.bn2", planes, planes, 3, stride, 1, h, h)
                     c3 = ConvBN(f"{p}.conv3", f"{p}.bn3", planes, planes * 4, 1, 1, 0, c2.hout, c2.wout)
                     convs, cout = [c1, c2, c3], planes * 4
-                shortcut = None
+                shortcut = sc_kind = None
                 if blk.downsample is not None:
-                    hs = h // stride
-                    shortcut = ConvBN(f"{p}.downsample.1", f"{p}.downsample.2", cin, cout, 1, 1, 0, hs, hs)
-                self.blocks.append(Block(convs, shortcut, stride, cin, h, h))
+                    # the shortcut's form and state_dict names from its modules: 'C' = [AvgPool2d, conv, BN] (downsample.1 / .2), 'B' = [conv, BN] (.0 / .1)
+                    mods = list(blk.downsample)
+                    ci = next(i for i, m in enumerate(mods) if isinstance(m, torch.nn.Conv2d))
+                    ni = next(i for i, m in enumerate(mods) if isinstance(m, torch.nn.BatchNorm2d))
+                    sc_kind = "C" if isinstance(mods[0], torch.nn.AvgPool2d) else "B"
+                    if sc_kind == "B" and mods[ci].stride[0] != stride:
+                        raise lib.EngineError(f"{p}.downsample: stride {mods[ci].stride} of the shortcut convolution in a block of stride {stride}")
+                    if stride not in (1, 2):
+                        raise lib.EngineError(f"{p}: stride {stride}")
+                    hs = h // stride if sc_kind == "C" else (h - 1) // stride + 1       # AvgPool2d floors; a strided 1x1 convolution samples 0, s, 2s, ...
+                    shortcut = ConvBN(f"{p}.downsample.{ci}", f"{p}.downsample.{ni}", cin, cout, 1, 1, 0, hs, hs)
+                self.blocks.append(Block(convs, shortcut, stride, cin, h, h, sc_kind))
                 cin, h = cout, convs[-1].hout
         self.feat, self.h_final = cin, h
         # "late bucket" of the arena: the parameters of the last stage and the classifier.  The backward pass finishes their gradients
@@ -455,7 +467,8 @@ class Engine:
             b.out = torch.empty_like(b.convs[-1].x)                              # block output (post add + ReLU)
             b.pooled = None
             if b.shortcut is not None and b.stride == 2:
-                b.pooled = torch.empty(n, b.hin // 2, b.win // 2, b.cin, device=dev, dtype=dt)
+                # the shortcut convolution's input: the 2x2 average ('C') or the pixels (2i, 2j) ('B') of the block input
+                b.pooled = torch.empty(n, b.shortcut.hin, b.shortcut.win, b.cin, device=dev, dtype=dt)
         self.feat = torch.empty(n, self.plan.feat, **f32)
         self.logits = torch.empty(n, self.plan.classes, **f32)
         self.dlogits = torch.empty(n, self.plan.classes, **f32)
@@ -748,7 +761,7 @@ class Engine:
         pooled_ready = False                         # the previous block's output pass already wrote this block's pooled input
         for bi, b in enumerate(plan.blocks):
             nxt = plan.blocks[bi + 1] if bi + 1 < len(plan.blocks) else None
-            next_pool = nxt.pooled if nxt is not None else None
+            next_pool = nxt.pooled if nxt is not None and nxt.kind != "B" else None     # (the fused copy is the AvgPool of 'C')
             a0 = a
             cur = a0
             for i, L in enumerate(b.convs):
@@ -760,7 +773,9 @@ class Engine:
             if b.shortcut is not None:
                 src = a0
                 if b.pooled is not None:
-                    if not pooled_ready:
+                    if b.kind == "B":                # the strided 1x1 convolution = the 1x1 stride-1 convolution below on the pixels it samples
+                        call("fb_subsample2_fwd", a0.data_ptr(), b.pooled.data_ptr(), G * self.chunk, b.hin, b.win, b.cin, self.dtc)
+                    elif not pooled_ready:
                         call("fb_avgpool2_fwd", a0.data_ptr(), b.pooled.data_ptr(), G * self.chunk, b.hin, b.win, b.cin, self.dtc)
                     src = b.pooled
                 self._conv_bn_fwd(b.shortcut, src, G, wsets, theta, pidx)
@@ -1006,7 +1021,15 @@ class Engine:
                 self._wgrad(S, src, dxs, G, gout)
                 d_p = self._dgrad(S, dxs, G, wsets)
                 pool.put(dxs, event=self._wgrad_event)
-                d_in = self._dgrad(first, cur_dx, G, wsets, addend=d_p, addend_mode=2 if b.pooled is not None else 1, bst=consumer)
+                if b.kind == "B" and b.pooled is not None:
+                    # the shortcut's input gradient lives on the pixels (2i, 2j) only: the input-gradient convolution runs without an addend (and
+                    # without the consumer's fused reduction: its output is not final), then fb_subsample2_bwd_add completes d_in in place --
+                    # same stream, after the convolution that writes d_in and before d_p goes back to the pool
+                    d_in = self._dgrad(first, cur_dx, G, wsets)
+                    call("fb_subsample2_bwd_add", d_in.data_ptr(), d_p.data_ptr(), n, b.hin, b.win, b.cin, self.dtc)
+                    self.amax_map.pop(d_in.data_ptr(), None)     # (fp16x2: magnitudes recorded for d_in before the add would be stale; _amax recomputes)
+                else:
+                    d_in = self._dgrad(first, cur_dx, G, wsets, addend=d_p, addend_mode=2 if b.pooled is not None else 1, bst=consumer)
                 pool.put(d_p)
             elif lazy:
                 d_in = self._dgrad(first, cur_dx, G, wsets, addend=d, addend_mode=1, addend_mask=out_bits, bst=consumer)

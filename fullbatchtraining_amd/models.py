@@ -30,10 +30,15 @@ def _conv(cin, cout, k, stride=1, pad=0):
 
 
 class _Shortcut(nn.Sequential):
-    """downsample 'C' (reference resnets.py:147-152): AvgPool2d(stride) -> 1x1 conv -> BN; indices 0,1,2."""
+    """downsample 'C' (reference resnets.py:147-152): AvgPool2d(stride) -> 1x1 conv -> BN; indices 0,1,2.
+    downsample 'B' (resnets.py:142-146, the constructor default and the He et al. / torchvision form): 1x1 conv with the block's stride -> BN;
+    indices 0,1.  (The engine's plan reads the form and the state_dict names off the modules.)"""
 
-    def __init__(self, cin, cout, stride):
-        super().__init__(nn.AvgPool2d(kernel_size=stride, stride=stride), _conv(cin, cout, 1), nn.BatchNorm2d(cout))
+    def __init__(self, cin, cout, stride, kind="C"):
+        if kind == "C":
+            super().__init__(nn.AvgPool2d(kernel_size=stride, stride=stride), _conv(cin, cout, 1), nn.BatchNorm2d(cout))
+        else:
+            super().__init__(_conv(cin, cout, 1, stride), nn.BatchNorm2d(cout))
 
 
 class BasicBlock(nn.Module):
@@ -80,8 +85,10 @@ class Bottleneck(nn.Module):
 class ResNet(nn.Module):
     def __init__(self, depth, channels, classes, stem="CIFAR", downsample="C"):
         super().__init__()
-        if downsample != "C":
-            raise NotImplementedError(f"downsample={downsample!r}: the engine implements the reference default 'C' only.")
+        if downsample not in ("B", "C"):
+            raise NotImplementedError(f"downsample={downsample!r}: the engine implements the shortcut forms 'B' (strided 1x1 conv -> BN) and "
+                                      "'C' (AvgPool2d -> 1x1 conv -> BN) only.")
+        self.downsample = downsample
         kind, stages = _LAYOUT[depth]
         block = BasicBlock if kind == "basic" else Bottleneck
         self.depth, self.kind, self.stem_kind, self.classes, self.channels = depth, kind, stem, classes, channels
@@ -98,7 +105,7 @@ class ResNet(nn.Module):
             stride = 1 if si == 0 else 2
             shortcut = None
             if stride != 1 or inplanes != width * block.expansion:
-                shortcut = _Shortcut(inplanes, width * block.expansion, stride)  # built before the block (RNG order)
+                shortcut = _Shortcut(inplanes, width * block.expansion, stride, downsample)  # built before the block (RNG order)
             blocks = [block(inplanes, width, stride, shortcut)]
             inplanes = width * block.expansion
             blocks += [block(inplanes, width, 1, None) for _ in range(1, nblocks)]

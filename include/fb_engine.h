@@ -254,6 +254,13 @@ int fb_stem_patches(const float* images, void* patches, int64_t n_img, int32_t C
 
 /* ---------------------------------------------------------------- pooling / head --------------------------------- */
 int fb_avgpool2_fwd(const void* x, void* y, int32_t n_img, int32_t H, int32_t W, int32_t C, int32_t dtype, void* stream);
+/* The spatial sampling of the strided 1x1 shortcut convolution (downsample 'B', resnets.py:142-146: conv1x1(stride 2) -> BN): the convolution
+ * itself runs as a 1x1 stride-1 fb_conv2d on the compacted copy.  fwd: y[n][i][j][:] = x[n][2i][2j][:], y is [n_img][(H+1)/2][(W+1)/2][C]
+ * (odd H, W allowed; a copy, bit-exact).  bwd_add, in place: dx[n][2i][2j][:] += dy[n][i][j][:], summed in fp32 and rounded once to `dtype`;
+ * every other element of dx is neither read nor written; one owner thread per element (deterministic).  16-byte vectors along C: C must be
+ * a multiple of 4 (FB_F32) / 8 (FB_BF16) and the pointers 16-byte aligned, FB_ERR_ARG otherwise.  64-bit indexing (ABI v14). */
+int fb_subsample2_fwd(const void* x, void* y, int32_t n_img, int32_t H, int32_t W, int32_t C, int32_t dtype, void* stream);
+int fb_subsample2_bwd_add(void* dx, const void* dy, int32_t n_img, int32_t H, int32_t W, int32_t C, int32_t dtype, void* stream);
 /* MaxPool2d(3,2,1) of the 'standard' stem (resnets.py:78); bwd scatters through recomputed argmax */
 int fb_maxpool3s2_fwd(const void* x, void* y, int32_t n_img, int32_t H, int32_t W, int32_t C, int32_t dtype, void* stream);
 int fb_maxpool3s2_bwd(const void* x, const void* dy, void* dx, int32_t n_img, int32_t H, int32_t W, int32_t C, int32_t dtype,
