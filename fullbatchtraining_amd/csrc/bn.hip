@@ -262,9 +262,10 @@ static bool launch_bn_apply(const void* x, void* y, const float* scale, const fl
     return false;                                           // (the grid-stride form does not track the largest magnitude)
 }
 
-// fused AvgPool2d(2,2) output of fb_bn_apply: a 512-vector run of the span kernel must be exactly two image rows
+// fused AvgPool2d(2,2) output of fb_bn_apply: a 512-vector run of the span kernel must be exactly two image rows, and a pixel's horizontal neighbour
+// (C / 8 lanes away, fetched with a wave shuffle) must sit in the same 64-lane wave: C <= 256
 extern "C" int32_t fb_bn_apply_can_pool(int32_t C, int32_t W, int64_t pixels_per_group, int32_t dtype) {
-    return dtype == FB_BF16 && W > 0 && (W & 1) == 0 && (long long)W * C == 2048 && C % 8 == 0 && 256 % (C / 8) == 0 && pixels_per_group % (2 * W) == 0;
+    return dtype == FB_BF16 && W > 0 && (W & 1) == 0 && (long long)W * C == 2048 && C % 8 == 0 && C / 8 <= 32 && 256 % (C / 8) == 0 && pixels_per_group % (2 * W) == 0;
 }
 
 extern "C" int fb_bn_apply(const void* x, void* y, const float* scale, const float* shift, const void* res, const float* rscale,
@@ -275,7 +276,7 @@ extern "C" int fb_bn_apply(const void* x, void* y, const float* scale, const flo
     const int64_t n_groups = (n_pixels + pixels_per_group - 1) / pixels_per_group;
     if (C % 8 != 0) FB_FAIL(FB_ERR_SHAPE, "fb_bn_apply: C=%d must be a multiple of 8", C);
     if (pool_out && !fb_bn_apply_can_pool(C, pool_W, pixels_per_group, dtype))
-        FB_FAIL(FB_ERR_UNSUPPORTED, "fb_bn_apply: fused 2x2 average pooling needs bf16, W * C == 2048 and whole row pairs per group (C=%d W=%d)", C, pool_W);
+        FB_FAIL(FB_ERR_UNSUPPORTED, "fb_bn_apply: fused 2x2 average pooling needs bf16, W * C == 2048, C <= 256 and whole row pairs per group (C=%d W=%d)", C, pool_W);
     const int32_t info[FB_PROF_INFO] = {(int32_t)(n_pixels / 128), C, (int32_t)(pixels_per_group / 128), dtype, res ? 1 : 0, mask_out ? 1 : 0, 0, pool_out ? 1 : 0, 0, 0, 0};
     const int prof = fb_prof_begin(FB_PROF_BN_APPLY, (hipStream_t)stream, info);
     bool tracked = false;

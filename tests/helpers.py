@@ -491,3 +491,166 @@ def eval_state(model, spec, x, seed=11, stat_images=32):
             sd[f"{bn}.running_mean"].copy_((buffers[f"{bn}.running_mean"] / orc.BN_MOMENTUM).float().cpu())
             sd[f"{bn}.running_var"].copy_(rv)
     return eps_ch
+
+
+# ----------------------------------------------------------------------------------------------------------------------------------
+# Confinement: a launch may read its inputs and write its outputs, and nothing else.  ``confined`` carves every operand out of the middle of a
+# byte slab of its own, runs the launch once per fill byte with the guard bands (and the outputs' prior content) filled with that byte, and
+# holds the launch to four properties: reads confined (same output bits whatever surrounds the operands), outputs fully defined (same bits
+# whatever the outputs held before; finite), writes confined (guards and stride gaps still hold the fill), inputs unchanged.  Works on
+# tensors of any device: tests/test_cpu_confinement.py plants each error in plain torch functions, tests/test_gpu_confinement.py runs the kernels.
+GUARD_BYTES = 256 * 4096 * 4      # the largest tile any kernel stages at the shapes of the tests: 256 pixels x 4096 channels x 4 B = 4 MiB, so
+                                  # a prefetch of one whole tile past an operand's end still lands in the guard (derived, not measured)
+FILLS = (0x00, 0xFF, 0x7F)        # 0xFF..: NaN in bf16 and fp32, -1 as a label or index; 0x7F..: a huge finite value (3.4e38) in both.  Both
+                                  # are needed: fmaxf(NaN, 0) hides a stray NaN, it does not hide a stray 3e38
+
+
+class ConfinementError(AssertionError):
+    pass
+
+
+class Strided:
+    """An operand of ``rows`` rows of ``width`` elements, ``stride`` elements apart (a slab of the [g][P] gradient arena, columns of a
+    statistics table, parameter rows): carved as ONE slab; the gaps between the rows are filled and checked like guards.  ``data``
+    ([rows, width]) for inputs and inout operands.  The launch receives a [rows, width] view with strides (stride, 1)."""
+
+    def __init__(self, rows, width, stride, dtype=torch.float32, data=None):
+        assert stride >= width and rows >= 1
+        self.rows, self.width, self.stride, self.dtype, self.data = int(rows), int(width), int(stride), dtype, data
+
+
+class _Slab:
+    def __init__(self, name, spec, device, guard):
+        self.name, self.guard = name, guard
+        if isinstance(spec, Strided):
+            self.dtype, self.data = spec.dtype, spec.data
+            self.shape, self.stride = (spec.rows, spec.width), spec.stride
+            n_el = (spec.rows - 1) * spec.stride + spec.width
+        else:
+            if torch.is_tensor(spec):
+                self.dtype, self.data, self.shape = spec.dtype, spec, tuple(spec.shape)
+            else:
+                shape, self.dtype = spec
+                self.data, self.shape = None, tuple(int(s) for s in (shape if isinstance(shape, (tuple, list)) else (shape,)))
+            self.stride = None
+            n_el = 1
+            for s in self.shape:
+                n_el *= s
+        self.item = torch.empty((), dtype=self.dtype).element_size()
+        self.nbytes = n_el * self.item
+        self.buf = torch.empty(guard + self.nbytes + guard, dtype=torch.uint8, device=device)
+        mid = self.buf[guard:guard + self.nbytes].view(self.dtype)
+        if self.stride is None:
+            self.view, self.gap = mid.view(self.shape), None
+        else:
+            self.view = torch.as_strided(mid, self.shape, (self.stride, 1))
+            gap = torch.ones(n_el, dtype=torch.bool, device=device)
+            torch.as_strided(gap, self.shape, (self.stride, 1)).fill_(False)
+            self.gap = gap.repeat_interleave(self.item) if gap.any() else None
+        if self.data is not None:
+            self.data = self.data.detach().to(device=device, dtype=self.dtype).reshape(self.shape).contiguous()
+
+    def arm(self, guard_fill, content_fill):
+        g = self.guard
+        self.buf[:g].fill_(guard_fill)
+        self.buf[g + self.nbytes:].fill_(guard_fill)
+        self.buf[g:g + self.nbytes].fill_(guard_fill if self.gap is not None else content_fill)
+        if self.gap is not None and self.data is None:
+            rows, width = self.shape
+            torch.as_strided(self.buf[g:g + self.nbytes], (rows, width * self.item), (self.stride * self.item, 1)).fill_(content_fill)
+        if self.data is not None:
+            self.view.copy_(self.data)
+
+    def bytes_now(self):
+        return self.view.contiguous().reshape(-1).view(torch.uint8).clone()
+
+    def touched(self, fill):
+        """None, or where a byte outside the operand no longer holds ``fill``."""
+        g = self.guard
+        for what, part, base in (("the guard before it", self.buf[:g], -g), ("the guard behind it", self.buf[g + self.nbytes:], self.nbytes)):
+            bad = part != fill
+            if bool(bad.any()):
+                first = int(bad.nonzero()[0])
+                return f"{what} (byte {base + first:+d} relative to the operand's first byte, {int(bad.sum())} bytes in all)"
+        if self.gap is not None:
+            bad = (self.buf[g:g + self.nbytes] != fill) & self.gap
+            if bool(bad.any()):
+                first = int(bad.nonzero()[0])
+                return (f"the gap between its rows (byte {first} = row {first // (self.stride * self.item)}, element "
+                        f"{first % (self.stride * self.item) // self.item} of the stride; {int(bad.sum())} bytes in all)")
+        return None
+
+
+def confined(fn, inputs, outputs, inout=(), device="cuda", scratch=(), fills=FILLS, guard=GUARD_BYTES):
+    """Run ``fn(ops)`` once per fill byte with every operand carved out of its own slab and assert that the launch is confined to its operands.
+
+    ``inputs``: {name: tensor | Strided(data=...)}; ``outputs``: {name: (shape, dtype) | Strided}; ``inout``: {name: tensor | Strided(data=...)} --
+    accumulators, counters and workspaces that must hold defined content at launch: restored before every run, only their surroundings are filled;
+    ``scratch``: {name: (shape, dtype)} -- workspaces whose content after the launch means nothing (filled like an output before it, not compared).
+    ``fn`` gets {name: view on ``device``} and must leave the work finished or on the current stream.  Returns {name: result of the FIRST run} for
+    the outputs and inout operands (clones)."""
+    inputs, outputs, inout, scratch = dict(inputs), dict(outputs), dict(inout), dict(scratch)
+    slabs = {}
+    for group in (inputs, outputs, inout, scratch):
+        for name, spec in group.items():
+            assert name not in slabs, f"operand name {name!r} used twice"
+            slabs[name] = _Slab(name, spec, device, guard)
+    for name in list(inputs) + list(inout):
+        assert slabs[name].data is not None, f"{name!r} needs content"
+    results = list(outputs) + list(inout)
+    is_cuda = torch.device(device).type == "cuda"
+
+    def run(guard_fill, content_fill):
+        for s in slabs.values():
+            s.arm(guard_fill, content_fill)
+        fn({name: s.view for name, s in slabs.items()})
+        if is_cuda:
+            torch.cuda.synchronize()
+        return {name: slabs[name].bytes_now() for name in results}
+
+    def where(a, b, s):
+        i = int((a != b).nonzero()[0]) // s.item
+        return i, int((a != b).view(-1, s.item).any(1).sum())
+
+    first, first_fill = None, None
+    for fill in fills:
+        got = run(fill, fill)
+        for name, s in slabs.items():                                           # writes confined
+            hit = s.touched(fill)
+            if hit is not None:
+                raise ConfinementError(f"writes confined: the launch wrote outside operand {name!r}: {hit}; fill 0x{fill:02X}")
+        for name in inputs:                                                     # inputs unchanged
+            s = slabs[name]
+            now, want = s.bytes_now(), s.data.reshape(-1).view(torch.uint8)
+            if not torch.equal(now, want):
+                i, cnt = where(now, want, s)
+                raise ConfinementError(f"inputs unchanged: the launch modified input {name!r} (element {i}, {cnt} elements in all); fill 0x{fill:02X}")
+        if first is None:
+            first, first_fill = got, fill
+            continue
+        for name in results:
+            if torch.equal(got[name], first[name]):
+                continue
+            s = slabs[name]
+            i, cnt = where(got[name], first[name], s)
+            stale = all(bool((r[name][i * s.item:(i + 1) * s.item] == f).all()) for r, f in ((first, first_fill), (got, fill)))
+            if name in outputs and stale:
+                raise ConfinementError(f"outputs fully defined: element {i} of output {name!r} is never written ({cnt} elements differ between "
+                                       f"fill 0x{first_fill:02X} and fill 0x{fill:02X}; it still holds the fill)")
+            # which memory does the result depend on: what surrounds the operands, or what the outputs held before?  The surroundings of the first run,
+            # the prior content of this one
+            probe = run(first_fill, fill)
+            if torch.equal(probe[name], first[name]):
+                raise ConfinementError(f"reads confined: {name!r} depends on memory outside the operands: element {i} ({cnt} elements in all) differs "
+                                       f"between fill 0x{first_fill:02X} and fill 0x{fill:02X} of the guards")
+            raise ConfinementError(f"outputs fully defined: {name!r} depends on what the outputs held before the launch (read-modify-write): element {i} "
+                                   f"({cnt} elements in all) differs between fill 0x{first_fill:02X} and fill 0x{fill:02X}")
+    out = {}
+    for name in results:
+        s = slabs[name]
+        t = first[name].view(s.dtype).view(s.shape)
+        if t.is_floating_point() and not bool(torch.isfinite(t.float()).all()):
+            i = int((~torch.isfinite(t.float().reshape(-1))).nonzero()[0])
+            raise ConfinementError(f"outputs fully defined: {name!r} is not finite (element {i})")
+        out[name] = t
+    return out

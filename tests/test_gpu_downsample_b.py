@@ -15,7 +15,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests.helpers import SENTINEL, err_cos, flat64, make_data, oracle_device, rel_err, summarise, torch_bf16_chunk_grads
+from tests.helpers import confined, err_cos, flat64, make_data, oracle_device, rel_err, summarise, torch_bf16_chunk_grads
 
 pytestmark = pytest.mark.gpu
 
@@ -33,23 +33,11 @@ def dsb():
 
 
 # ------------------------------------------------------------------------------------------------------------------ kernels --
-GUARD = 4096       # elements behind the last one of every allocation: no kernel may touch them
-
-
-def _guarded(t, dtype):
-    """``t`` (host) in a device allocation of its own with a guard band of SENTINEL values behind it -> (whole buffer, view of the tensor)."""
-    buf = torch.full((t.numel() + GUARD,), SENTINEL, dtype=dtype, device="cuda")
-    buf[:t.numel()] = t.reshape(-1).to(dtype).cuda()
-    return buf, buf[:t.numel()].view(t.shape)
-
-
-def _guard_untouched(buf, n, dtype):
-    return bool((buf[n:] == torch.tensor(SENTINEL, dtype=dtype, device="cuda")).all())
-
-
 @pytest.mark.parametrize("shape", [(3, 8, 8, 64), (2, 7, 7, 256), (5, 16, 16, 128)], ids=lambda s: "x".join(map(str, s)))
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
 def test_subsample_kernels_against_torch_slicing(dtype, shape):
+    """Through tests/helpers.py ``confined``: guard bands on both sides of every operand stay untouched, the inputs keep their bytes, and the results do not
+    depend on what surrounds the operands (nor, for the copy, on what the output held before)."""
     from fullbatchtraining_amd import lib
 
     n, H, W, C = shape
@@ -57,28 +45,19 @@ def test_subsample_kernels_against_torch_slicing(dtype, shape):
     dtc = lib.dtype_code(dtype)
     gen = torch.Generator().manual_seed(17 + H + C)
     x = torch.randn(n, H, W, C, generator=gen).to(dtype)
-    xb, xd = _guarded(x, dtype)
-    yb, yd = _guarded(torch.full((n, Ho, Wo, C), -7.0), dtype)
-    lib.call("fb_subsample2_fwd", xd.data_ptr(), yd.data_ptr(), n, H, W, C, dtc)
-    torch.cuda.synchronize()
-    assert torch.equal(yd.cpu(), x[:, ::2, ::2])                                     # a copy: bit-exact
-    assert torch.equal(xd.cpu(), x) and _guard_untouched(xb, x.numel(), dtype) and _guard_untouched(yb, yd.numel(), dtype)
-    # in-place scatter-add: fp32 sum, one rounding to the storage type
+    y = confined(lambda o: lib.call("fb_subsample2_fwd", o["x"].data_ptr(), o["y"].data_ptr(), n, H, W, C, dtc), {"x": x}, {"y": ((n, Ho, Wo, C), dtype)})["y"]
+    assert torch.equal(y.cpu(), x[:, ::2, ::2])                                      # a copy: bit-exact
+    # in-place scatter-add: fp32 sum, one rounding to the storage type (dx is an accumulator: it keeps its content, its surroundings are filled)
     dx = torch.randn(n, H, W, C, generator=gen).to(dtype)
     dy = (torch.randn(n, Ho, Wo, C, generator=gen) * 1.7).to(dtype)
     want = dx.clone()
     want[:, ::2, ::2] = (dx.float()[:, ::2, ::2] + dy.float()).to(dtype)
-    dxb, dxd = _guarded(dx, dtype)
-    dyb, dyd = _guarded(dy, dtype)
-    lib.call("fb_subsample2_bwd_add", dxd.data_ptr(), dyd.data_ptr(), n, H, W, C, dtc)
-    torch.cuda.synchronize()
-    got = dxd.cpu()
+    got = confined(lambda o: lib.call("fb_subsample2_bwd_add", o["dx"].data_ptr(), o["dy"].data_ptr(), n, H, W, C, dtc), {"dy": dy}, {}, inout={"dx": dx})["dx"].cpu()
     assert torch.equal(got[:, ::2, ::2], want[:, ::2, ::2])
     rest = torch.ones(H, W, dtype=torch.bool)
     rest[::2, ::2] = False
     assert torch.equal(got[:, rest], dx[:, rest])                                    # every other position: the bits from before
-    assert not torch.equal(got, dx) and torch.equal(dyd.cpu(), dy)
-    assert _guard_untouched(dxb, dx.numel(), dtype) and _guard_untouched(dyb, dy.numel(), dtype)
+    assert not torch.equal(got, dx)
 
 
 @pytest.mark.parametrize("dtype,C", [(torch.float32, 66), (torch.bfloat16, 68)], ids=["f32-66", "bf16-68"])

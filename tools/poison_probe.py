@@ -3,6 +3,10 @@ launch is repeated with zeroed surroundings, and the two results must be bit-ide
 and lets the value reach its result (e.g. masks it by a multiplication) shows up here deterministically.
 
     python tools/poison_probe.py
+
+The suite's automatic form of this check is tests/test_gpu_confinement.py (tests/helpers.py ``confined``): every launch form and storage type,
+writes as well as reads (guard bands and stride gaps), never-written output elements, and a 0x7F fill next to the NaN one.  This tool stays
+for the larger hand-run sweep of image counts.
 """
 import os
 import sys
