@@ -11,6 +11,7 @@
 #include <stdlib.h>
 
 #include <memory>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -38,20 +39,96 @@ template <typename... A, int (*f)(A...)> struct Bind<int (*)(A...), f> {
     static int call(const uint64_t* w, void* st) { return run(w, st, std::index_sequence_for<A...>{}); }
 };
 
-struct Entry { const char* name; Thunk fn; int nargs; };
-#define FB_ENTRY(name) {#name, &Bind<decltype(&name), &name>::call, Bind<decltype(&name), &name>::N}
-// every asynchronous entry point whose arguments are scalars, device pointers or ONE leading argument struct (copied into the list)
-const Entry kEntries[] = {
-    FB_ENTRY(fb_conv2d), FB_ENTRY(fb_conv2d_wgrad), FB_ENTRY(fb_absmax), FB_ENTRY(fb_wgrad_reduce), FB_ENTRY(fb_weight_prep),
-    FB_ENTRY(fb_bn_fwd_finalize), FB_ENTRY(fb_bn_apply), FB_ENTRY(fb_bn_running_update), FB_ENTRY(fb_bn_bwd_reduce),
-    FB_ENTRY(fb_bn_bwd_finalize), FB_ENTRY(fb_bn_bwd_apply), FB_ENTRY(fb_avgpool2_fwd), FB_ENTRY(fb_maxpool3s2_fwd),
-    FB_ENTRY(fb_maxpool3s2_bwd), FB_ENTRY(fb_head_pool), FB_ENTRY(fb_head_loss), FB_ENTRY(fb_head_bwd), FB_ENTRY(fb_mt_sqnorm),
-    FB_ENTRY(fb_mt_accumulate), FB_ENTRY(fb_mt_fd_perturb), FB_ENTRY(fb_mt_fd_combine_accumulate), FB_ENTRY(fb_mt_fd_combine),
-    FB_ENTRY(fb_mt_chunk_clip), FB_ENTRY(fb_bn_eval_coeffs), FB_ENTRY(fb_mt_norms2), FB_ENTRY(fb_mt_clip_sgd), FB_ENTRY(fb_mt_scale), FB_ENTRY(fb_bn_bwd_fused), FB_ENTRY(fb_bn_bwd_reduce2), FB_ENTRY(fb_bn_bwd_apply2),
-    FB_ENTRY(fb_conv2d_wgrad_chain), FB_ENTRY(fb_mt_accumulate_sum), FB_ENTRY(fb_mt_accumulate_skip),
-    FB_ENTRY(fb_maxpool3s2_fwd_idx), FB_ENTRY(fb_maxpool3s2_bwd_idx), FB_ENTRY(fb_subsample2_fwd), FB_ENTRY(fb_subsample2_bwd_add),
+// ---- the ABI described by the compiler: one row per function of fb_engine.h, the source of every host binding (fb_entry_*) --------------
+template <typename T> constexpr char sig_code() {
+    if constexpr (std::is_void_v<T>) return 'v';
+    else if constexpr (std::is_same_v<T, int32_t>) return 'i';
+    else if constexpr (std::is_same_v<T, int64_t>) return 'l';
+    else if constexpr (std::is_same_v<T, float>) return 'f';
+    else if constexpr (std::is_same_v<T, double>) return 'd';
+    else if constexpr (std::is_same_v<T, const fb_conv_args*>) return 'C';
+    else if constexpr (std::is_same_v<T, const fb_wgrad_args*>) return 'W';
+    else if constexpr (std::is_same_v<T, const char*>) return 's';
+    else if constexpr (std::is_pointer_v<T>) return 'p';
+    else static_assert(sizeof(T) == 0, "fb_engine.h uses a type that has no signature code");
+}
+// Sig<decltype(&f)>::str: "<return>:<arguments>", e.g. fb_conv2d "i:Cp"
+template <typename F> struct Sig;
+template <typename R, typename... A> struct Sig<R (*)(A...)> {
+    static constexpr char str[] = {sig_code<R>(), ':', sig_code<A>()..., '\0'};
+};
+constexpr bool is_launch_sig(const char* s) {      // int f(..., void* stream)
+    int n = 0;
+    while (s[n]) ++n;
+    return n >= 3 && s[0] == 'i' && s[n - 1] == 'p';
+}
+
+enum { HOST = 0, LAUNCH = 1, RECORDABLE = 2 };     // fb_entry_kind
+struct Entry { const char* name; int32_t kind; const char* sig; Thunk fn; };
+#define FB_ROW(f, kind, thunk) {#f, kind, Sig<decltype(&f)>::str, thunk}
+#define FB_HOST(f) FB_ROW(f, HOST, nullptr)
+#define FB_LAUNCH(f) FB_ROW(f, LAUNCH, nullptr)
+// recordable: an asynchronous entry point whose arguments are scalars, device pointers or ONE leading argument struct (copied into the list)
+#define FB_RECORDABLE(f) FB_ROW(f, RECORDABLE, (&Bind<decltype(&f), &f>::call))
+constexpr Entry kEntries[] = {
+    FB_HOST(fb_last_error_string), FB_HOST(fb_abi_version), FB_HOST(fb_entry_count), FB_HOST(fb_entry_name), FB_HOST(fb_entry_sig),
+    FB_HOST(fb_entry_kind), FB_HOST(fb_struct_field), FB_HOST(fb_struct_size), FB_HOST(fb_abi_constant),
+    FB_HOST(fb_profile_enable), FB_HOST(fb_profile_read), FB_HOST(fb_profile_read_launches),
+    FB_HOST(fb_cmd_fn_id), FB_HOST(fb_cmd_fn_nargs), FB_HOST(fb_event_new), FB_HOST(fb_event_count), FB_HOST(fb_event_record),
+    FB_HOST(fb_event_wait), FB_HOST(fb_cmdlist_create), FB_HOST(fb_cmdlist_destroy), FB_HOST(fb_cmdlist_size), FB_HOST(fb_cmdlist_add_call),
+    FB_HOST(fb_cmdlist_add_event), FB_HOST(fb_cmdlist_replay),
+    // convolution
+    FB_RECORDABLE(fb_conv2d), FB_HOST(fb_conv_masked_addend_supported), FB_HOST(fb_conv_bwd_stat_supported), FB_RECORDABLE(fb_absmax),
+    FB_HOST(fb_wgrad_bn_fused_supported), FB_RECORDABLE(fb_conv2d_wgrad), FB_HOST(fb_wgrad_chain_supported), FB_RECORDABLE(fb_conv2d_wgrad_chain),
+    FB_HOST(fb_ws_conv_stat_floats), FB_HOST(fb_ws_wgrad_slab_floats), FB_HOST(fb_ws_bn_partial_floats), FB_HOST(fb_ws_mt_floats),
+    FB_RECORDABLE(fb_wgrad_reduce), FB_RECORDABLE(fb_weight_prep),
+    // batch norm
+    FB_RECORDABLE(fb_bn_fwd_finalize), FB_RECORDABLE(fb_bn_apply), FB_HOST(fb_ws_bn_amax_floats), FB_HOST(fb_bn_apply_can_pool),
+    FB_RECORDABLE(fb_bn_running_update), FB_HOST(fb_bn_bwd_reduce_rows), FB_RECORDABLE(fb_bn_bwd_reduce), FB_RECORDABLE(fb_bn_bwd_finalize),
+    FB_RECORDABLE(fb_bn_bwd_apply), FB_RECORDABLE(fb_bn_bwd_reduce2), FB_RECORDABLE(fb_bn_bwd_apply2), FB_HOST(fb_bn_bwd_fused_supported),
+    FB_HOST(fb_ws_bn_bwd_fused_floats), FB_HOST(fb_ws_bn_bwd_fused_ints), FB_RECORDABLE(fb_bn_bwd_fused),
+    // data path (fb_stem_patches takes a HOST array), pooling, head
+    FB_LAUNCH(fb_stem_patches), FB_RECORDABLE(fb_avgpool2_fwd), FB_RECORDABLE(fb_subsample2_fwd), FB_RECORDABLE(fb_subsample2_bwd_add),
+    FB_RECORDABLE(fb_maxpool3s2_fwd), FB_RECORDABLE(fb_maxpool3s2_bwd), FB_RECORDABLE(fb_maxpool3s2_fwd_idx), FB_RECORDABLE(fb_maxpool3s2_bwd_idx),
+    FB_RECORDABLE(fb_head_pool), FB_RECORDABLE(fb_head_loss), FB_RECORDABLE(fb_bn_eval_coeffs), FB_LAUNCH(fb_head_tta), FB_RECORDABLE(fb_head_bwd),
+    // multi-tensor
+    FB_RECORDABLE(fb_mt_sqnorm), FB_RECORDABLE(fb_mt_accumulate), FB_RECORDABLE(fb_mt_accumulate_sum), FB_RECORDABLE(fb_mt_accumulate_skip),
+    FB_RECORDABLE(fb_mt_fd_perturb), FB_RECORDABLE(fb_mt_fd_combine_accumulate), FB_RECORDABLE(fb_mt_fd_combine), FB_RECORDABLE(fb_mt_chunk_clip),
+    FB_RECORDABLE(fb_mt_norms2), FB_RECORDABLE(fb_mt_clip_sgd), FB_RECORDABLE(fb_mt_scale), FB_LAUNCH(fb_mt_sam_ascent), FB_LAUNCH(fb_mt_sam_restore),
+    FB_LAUNCH(fb_mt_absmax2), FB_LAUNCH(fb_mt_pnorm2), FB_LAUNCH(fb_mt_norm_bias), FB_LAUNCH(fb_mt_ema), FB_LAUNCH(fb_mt_clip_scale),
+    FB_LAUNCH(fb_mt_grad_noise),
 };
 constexpr int kNumEntries = sizeof(kEntries) / sizeof(kEntries[0]);
+constexpr bool launches_take_a_stream() {
+    for (const Entry& e : kEntries)
+        if (e.kind != HOST && !is_launch_sig(e.sig)) return false;
+    return true;
+}
+static_assert(launches_take_a_stream(), "a launch row whose function is not int f(..., void* stream)");
+inline bool recordable(int32_t fn) { return fn >= 0 && fn < kNumEntries && kEntries[fn].kind == RECORDABLE; }
+inline int nargs_of(const Entry& e) { return (int)strlen(e.sig) - 2; }      // (including the stream)
+
+// ---- the argument structs, field by field in header order ----------------------------------------------------------------------------
+struct Field { const char* name; int32_t offset, size; char code; };
+#define FB_FIELD(S, f) {#f, (int32_t)offsetof(S, f), (int32_t)sizeof(S::f), sig_code<decltype(S::f)>()}
+#define F(f) FB_FIELD(fb_conv_args, f)
+constexpr Field kConvFields[] = {F(src), F(wgt), F(dst), F(addend), F(stat_partial), F(n_img), F(Hs), F(Ws), F(Cs), F(Hd), F(Wd), F(Cd), F(R), F(S),
+                                 F(stride), F(pad), F(mode), F(imgs_per_wset), F(wset_stride), F(addend_mode), F(dtype), F(addend_mask), F(bst_x),
+                                 F(bst_mask), F(amax_src), F(amax_wgt), F(amax_imgs)};
+#undef F
+#define F(f) FB_FIELD(fb_wgrad_args, f)
+constexpr Field kWgradFields[] = {F(x), F(dy), F(dw_partial), F(n_img), F(Hs), F(Ws), F(Cs), F(Hd), F(Wd), F(Cd), F(R), F(S), F(stride), F(pad),
+                                  F(imgs_per_group), F(split_k), F(dtype), F(group_stride), F(amax_x), F(amax_dy), F(bn_x), F(bn_mask), F(bn_coef)};
+#undef F
+// a trailing field left out of a table: the last listed field then ends before the struct does
+template <size_t N> constexpr bool reaches_end(const Field (&f)[N], size_t align, size_t size) {
+    return (f[N - 1].offset + f[N - 1].size + align - 1) / align * align == size;
+}
+static_assert(reaches_end(kConvFields, alignof(fb_conv_args), sizeof(fb_conv_args)), "kConvFields does not reach the end of fb_conv_args");
+static_assert(reaches_end(kWgradFields, alignof(fb_wgrad_args), sizeof(fb_wgrad_args)), "kWgradFields does not reach the end of fb_wgrad_args");
+struct StructInfo { const Field* fields; int32_t n, size; };
+constexpr StructInfo kStructs[] = {{kConvFields, sizeof(kConvFields) / sizeof(Field), sizeof(fb_conv_args)},
+                                   {kWgradFields, sizeof(kWgradFields) / sizeof(Field), sizeof(fb_wgrad_args)}};
 
 enum { CMD_CALL = 0, CMD_EVENT_RECORD = 1, CMD_EVENT_WAIT = 2 };
 struct Cmd { int32_t kind, fn, stream, ev; uint32_t off, n; };
@@ -65,12 +142,36 @@ std::vector<hipEvent_t> g_events;   // process-wide event table: ids are shared 
 
 }  // namespace
 
-extern "C" int32_t fb_cmd_fn_id(const char* name) {
-    for (int i = 0; i < kNumEntries; ++i)
-        if (strcmp(kEntries[i].name, name) == 0) return i;
+extern "C" int32_t fb_entry_count(void) { return kNumEntries; }
+extern "C" const char* fb_entry_name(int32_t i) { return i >= 0 && i < kNumEntries ? kEntries[i].name : nullptr; }
+extern "C" const char* fb_entry_sig(int32_t i) { return i >= 0 && i < kNumEntries ? kEntries[i].sig : nullptr; }
+extern "C" int32_t fb_entry_kind(int32_t i) { return i >= 0 && i < kNumEntries ? kEntries[i].kind : -1; }
+extern "C" int32_t fb_struct_field(int32_t which, int32_t i, const char** name, int32_t* offset, int32_t* size, char* code) {
+    if (which < 0 || which > 1) FB_FAIL(FB_ERR_ARG, "fb_struct_field: unknown struct %d", which);
+    const StructInfo& s = kStructs[which];
+    if (i >= 0 && i < s.n) {
+        *name = s.fields[i].name;
+        *offset = s.fields[i].offset;
+        *size = s.fields[i].size;
+        *code = s.fields[i].code;
+    }
+    return s.n;
+}
+extern "C" int32_t fb_struct_size(int32_t which) { return which >= 0 && which <= 1 ? kStructs[which].size : -1; }
+extern "C" int32_t fb_abi_constant(const char* name) {
+    if (strcmp(name, "FB_MT_BLOCKS") == 0) return FB_MT_BLOCKS;
+    if (strcmp(name, "FB_PROF_CLASSES") == 0) return FB_PROF_CLASSES;
+    if (strcmp(name, "FB_PROF_INFO") == 0) return FB_PROF_INFO;
     return -1;
 }
-extern "C" int32_t fb_cmd_fn_nargs(int32_t fn) { return fn >= 0 && fn < kNumEntries ? kEntries[fn].nargs : -1; }
+
+// a recordable entry point's id is its row in the table
+extern "C" int32_t fb_cmd_fn_id(const char* name) {
+    for (int i = 0; i < kNumEntries; ++i)
+        if (kEntries[i].kind == RECORDABLE && strcmp(kEntries[i].name, name) == 0) return i;
+    return -1;
+}
+extern "C" int32_t fb_cmd_fn_nargs(int32_t fn) { return recordable(fn) ? nargs_of(kEntries[fn]) : -1; }
 
 // ---- events (timing disabled): cross-stream ordering of eager launches and of recorded lists alike ------------------------------
 extern "C" int32_t fb_event_new(void) {
@@ -105,8 +206,8 @@ extern "C" int64_t fb_cmdlist_size(const void* cl) { return cl ? (int64_t)((cons
 extern "C" int fb_cmdlist_add_call(void* handle, int32_t fn, const uint64_t* words, int32_t n_words, int32_t stream_idx, const void* blob,
                                    int32_t blob_bytes) {
     CmdList* cl = (CmdList*)handle;
-    if (!cl || fn < 0 || fn >= kNumEntries) FB_FAIL(FB_ERR_ARG, "fb_cmdlist_add_call: bad list or function id %d", fn);
-    if (n_words != kEntries[fn].nargs - 1) FB_FAIL(FB_ERR_ARG, "fb_cmdlist_add_call: %s takes %d words, got %d", kEntries[fn].name, kEntries[fn].nargs - 1, n_words);
+    if (!cl || !recordable(fn)) FB_FAIL(FB_ERR_ARG, "fb_cmdlist_add_call: bad list or function id %d", fn);
+    if (n_words != nargs_of(kEntries[fn]) - 1) FB_FAIL(FB_ERR_ARG, "fb_cmdlist_add_call: %s takes %d words, got %d", kEntries[fn].name, nargs_of(kEntries[fn]) - 1, n_words);
     Cmd c{CMD_CALL, fn, stream_idx, -1, (uint32_t)cl->words.size(), (uint32_t)n_words};
     cl->words.insert(cl->words.end(), words, words + n_words);
     if (blob && blob_bytes > 0) {

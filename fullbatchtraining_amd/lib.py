@@ -10,8 +10,7 @@ import struct
 import torch
 
 FB_F32, FB_BF16 = 0, 1
-EXPECTED_ABI = 14         # fb_abi_version() the ctypes structs / signatures below were written for
-MT_BLOCKS = 1024
+EXPECTED_ABI = 15         # fb_abi_version() this package was written for (older libraries lack the entry-point table load() binds from)
 _LIB_PATH = os.environ.get("FB_LIB_PATH") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "libfbengine.so")     # (FB_LIB_PATH: A/B builds, tools/build_variant.py)
 
 c_void_p, c_int, c_i64, c_float, c_double = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_double
@@ -33,79 +32,26 @@ class WgradArgs(C.Structure):
                 ("bn_x", c_void_p), ("bn_mask", c_void_p), ("bn_coef", c_void_p)]
 
 
-_SIGS = {
-    "fb_conv2d": [C.POINTER(ConvArgs), c_void_p],
-    "fb_conv2d_wgrad": [C.POINTER(WgradArgs), c_void_p],
-    "fb_absmax": [c_void_p, c_i64, c_int, c_i64, c_int, c_void_p, c_void_p],
-    "fb_wgrad_reduce": [c_void_p, c_void_p, c_i64, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
-    "fb_weight_prep": [c_void_p, c_i64, c_i64, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p],
-    "fb_bn_fwd_finalize": [c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_i64, c_float, c_void_p, c_void_p, c_int,
-                           c_int, c_void_p, c_void_p, c_void_p, c_void_p],
-    "fb_bn_apply": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_int, c_i64, c_i64, c_int, c_void_p, c_void_p, c_int,
-                    c_int, c_void_p, c_void_p, c_void_p],
-    "fb_bn_running_update": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_i64, c_void_p, c_int, c_int, c_float, c_void_p],
-    "fb_bn_bwd_reduce": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_i64, c_int, c_i64, c_int, c_void_p],
-    "fb_bn_bwd_finalize": [c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
-                           c_i64, c_void_p, c_int, c_void_p],
-    "fb_bn_bwd_apply": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_int, c_i64, c_int, c_void_p, c_void_p, c_void_p],
-    "fb_bn_bwd_reduce2": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_i64, c_int, c_i64, c_int,
-                          c_void_p],
-    "fb_bn_bwd_apply2": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_int, c_i64, c_int, c_void_p],
-    "fb_bn_bwd_fused": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_void_p,
-                        c_i64, c_int, c_i64, c_double, c_int, c_void_p, c_void_p, c_void_p],
-    "fb_stem_patches": [c_void_p, c_void_p, c_i64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int,
-                        C.POINTER(c_float), c_int, c_void_p],
-    "fb_avgpool2_fwd": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p],
-    "fb_subsample2_fwd": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p],
-    "fb_subsample2_bwd_add": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p],
-    "fb_maxpool3s2_fwd": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p],
-    "fb_maxpool3s2_bwd": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p],
-    "fb_maxpool3s2_fwd_idx": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p],
-    "fb_maxpool3s2_bwd_idx": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p],
-    "fb_head_pool": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p],
-    "fb_head_loss": [c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
-                     c_float, c_int, c_void_p],
-    "fb_head_bwd": [c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_i64, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
-                    c_void_p],
-    "fb_mt_sqnorm": [c_void_p, c_i64, c_int, c_i64, c_float, c_void_p, c_float, c_void_p, c_void_p, c_void_p],
-    "fb_mt_accumulate": [c_void_p, c_void_p, c_i64, c_int, c_i64, c_int, c_void_p, c_void_p, c_void_p],
-    "fb_mt_fd_perturb": [c_void_p, c_void_p, c_i64, c_int, c_i64, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p, c_float, c_void_p,
-                         c_void_p],
-    "fb_mt_fd_combine_accumulate": [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_int, c_i64, c_void_p, c_float, c_int, c_void_p],
-    "fb_mt_fd_combine": [c_void_p, c_void_p, c_void_p, c_i64, c_int, c_i64, c_void_p, c_float, c_void_p],
-    "fb_mt_chunk_clip": [c_void_p, c_i64, c_int, c_i64, c_void_p, c_float, c_void_p, c_void_p],
-    "fb_bn_eval_coeffs": [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int, c_void_p],
-    "fb_head_tta": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
-    "fb_mt_norms2": [c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_void_p],
-    "fb_mt_clip_sgd": [c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_float, c_float, c_float, c_float, c_float, c_int, c_int, c_void_p],
-    "fb_mt_scale": [c_void_p, c_i64, c_float, c_void_p],
-    "fb_mt_sam_ascent": [c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_float, c_float, c_void_p],
-    "fb_mt_sam_restore": [c_void_p, c_void_p, c_i64, c_void_p],
-    "fb_mt_absmax2": [c_void_p, c_i64, c_void_p, c_void_p, c_void_p],
-    "fb_mt_pnorm2": [c_void_p, c_i64, c_float, c_void_p, c_void_p, c_void_p],
-    "fb_mt_norm_bias": [c_void_p, c_void_p, c_i64, c_void_p, c_float, c_float, c_int, c_void_p],
-    "fb_mt_ema": [c_void_p, c_void_p, c_i64, c_float, c_float, c_void_p],
-    "fb_mt_clip_scale": [c_void_p, c_i64, c_void_p, c_float, c_void_p],
-    "fb_mt_grad_noise": [c_void_p, c_void_p, c_i64, c_float, c_int, c_void_p],
-    "fb_conv2d_wgrad_chain": [C.POINTER(WgradArgs), c_int, c_void_p, c_void_p, c_void_p],
-    "fb_mt_accumulate_sum": [c_void_p, c_void_p, c_i64, c_int, c_int, c_void_p],
-    "fb_mt_accumulate_skip": [c_void_p, c_void_p, c_i64, c_int, c_i64, c_int, c_void_p, c_void_p] + [c_i64] * 8 + [c_void_p],
-}
-EXPORTS = tuple(_SIGS) + ("fb_last_error_string", "fb_abi_version", "fb_profile_enable", "fb_profile_read", "fb_ws_conv_stat_floats",
-                          "fb_ws_wgrad_slab_floats", "fb_ws_bn_partial_floats", "fb_ws_mt_floats", "fb_bn_bwd_reduce_rows", "fb_conv_masked_addend_supported", "fb_conv_bwd_stat_supported",
-                          "fb_bn_apply_can_pool", "fb_ws_bn_amax_floats", "fb_profile_read_launches", "fb_cmd_fn_id", "fb_cmd_fn_nargs", "fb_event_new", "fb_event_count", "fb_bn_bwd_fused_supported", "fb_ws_bn_bwd_fused_floats", "fb_ws_bn_bwd_fused_ints", "fb_wgrad_bn_fused_supported", "fb_wgrad_chain_supported",
-                          "fb_event_record", "fb_event_wait", "fb_cmdlist_create", "fb_cmdlist_destroy", "fb_cmdlist_size", "fb_cmdlist_add_call",
-                          "fb_cmdlist_add_event", "fb_cmdlist_replay")
+# signature codes of the library's entry-point table (fb_entry_sig, include/fb_engine.h) -> ctypes
+_CTYPES = {"v": None, "i": c_int, "l": c_i64, "f": c_float, "d": c_double, "p": c_void_p, "s": C.c_char_p,
+           "C": C.POINTER(ConvArgs), "W": C.POINTER(WgradArgs)}
 PROF_CLASSES = ("igemm_fwd", "igemm_dgrad", "wgrad", "bn_apply", "bn_bwd_reduce", "bn_bwd_apply", "bn_bwd_fused")
-PROF_INFO = 11
 PROF_KERNELS = {0: "?", 1: "conv_igemm_kernel (register-staged)", 2: "conv_igemm_v3_kernel", 3: "conv3x3s1_halo4_kernel", 4: "conv3x3s1_c64_halo5_kernel",
                 5: "conv3x3s2_dgrad_quad_kernel", 6: "conv1x1_k32_kernel", 7: "conv1x1_stream_kernel", 8: "conv3x3s2_fwd_kernel", 9: "conv1x1_pipe_kernel", 10: "conv1x1_gemm_kernel",
                 16: "conv_wgrad_kernel", 17: "conv_wgrad3x3_kernel", 18: "conv_wgrad3x3_v2_kernel", 19: "conv_wgrad1x1_kernel"}
+# filled by load() from the library: EXPORTS (every entry point), _SIGS (launch -> ctypes argument types, stream included), MT_BLOCKS, PROF_INFO
+_FROM_LIBRARY = ("EXPORTS", "_SIGS", "_ARG_CODES", "MT_BLOCKS", "PROF_INFO")
+
+
+def __getattr__(name):
+    if name in _FROM_LIBRARY:
+        load()
+        return globals()[name]
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 def profile_enable(on, capacity=32768):
     lib = load()
-    lib.fb_profile_enable.argtypes, lib.fb_profile_enable.restype = [c_int, c_int], c_int
     if lib.fb_profile_enable(1 if on else 0, capacity) != 0:
         raise EngineError(lib.fb_last_error_string().decode())
 
@@ -113,7 +59,6 @@ def profile_enable(on, capacity=32768):
 def profile_read():
     """-> {class: (ms, launches, dropped)} for launches recorded since the previous read (synchronises on them)."""
     lib = load()
-    lib.fb_profile_read.argtypes = [C.POINTER(c_double), C.POINTER(c_i64), C.POINTER(c_i64)]
     k = len(PROF_CLASSES)
     ms, n, d = (c_double * k)(), (c_i64 * k)(), (c_i64 * k)()
     if lib.fb_profile_read(ms, n, d) != 0:
@@ -121,12 +66,10 @@ def profile_read():
     return {k: (ms[i], n[i], d[i]) for i, k in enumerate(PROF_CLASSES)}
 
 
-
 def profile_read_launches(cap=1 << 18):
     """-> list of (class name, shape words tuple, ms) for every launch recorded since the previous ``profile_read`` (call this first:
     ``profile_read`` resets the records)."""
     lib = load()
-    lib.fb_profile_read_launches.argtypes, lib.fb_profile_read_launches.restype = [C.POINTER(c_int), C.POINTER(c_float), c_i64], c_i64
     info, ms = (c_int * (cap * (PROF_INFO + 1)))(), (c_float * cap)()
     n = lib.fb_profile_read_launches(info, ms, cap)
     if n < 0:
@@ -142,48 +85,61 @@ class EngineError(RuntimeError):
     pass
 
 
+def check_layout(cls, fields, size):
+    """Raises unless the ctypes Structure ``cls`` has the C layout ``fields`` = [(name, offset, size, code)] (fb_struct_field, in
+    declaration order) of ``size`` bytes; the fields themselves must follow each other at their natural alignment."""
+    mine, end = cls._fields_, 0
+    for i, (name, offset, nbytes, code) in enumerate(fields):
+        if offset != -(-end // nbytes) * nbytes:
+            raise EngineError(f"{cls.__name__}: the library's field {name} at offset {offset} does not follow its predecessor, which ends at {end}")
+        end = offset + nbytes
+        if i >= len(mine) or mine[i][0] != name:
+            raise EngineError(f"{cls.__name__}: field {i} is {name} in the library, {mine[i][0] if i < len(mine) else 'missing'} here")
+        here = getattr(cls, name)
+        if (here.offset, here.size) != (offset, nbytes) or mine[i][1] is not _CTYPES[code]:
+            raise EngineError(f"{cls.__name__}.{name}: {mine[i][1].__name__} of {here.size} bytes at offset {here.offset} here, "
+                              f"'{code}' of {nbytes} bytes at offset {offset} in the library")
+    if len(mine) > len(fields):
+        raise EngineError(f"{cls.__name__}: field {mine[len(fields)][0]} is not in the library's struct")
+    if C.sizeof(cls) != size:
+        raise EngineError(f"{cls.__name__}: {C.sizeof(cls)} bytes here, {size} in the library")
+
+
+def _struct_fields(lib, which):
+    name, offset, nbytes, code = C.c_char_p(), c_int(), c_int(), C.c_char()
+    out = []
+    while len(out) < lib.fb_struct_field(which, len(out), C.byref(name), C.byref(offset), C.byref(nbytes), C.byref(code)):
+        out.append((name.value.decode(), offset.value, nbytes.value, code.value.decode()))
+    return out
+
+
 def load():
-    """Load the shared library (no compute).  Raises if it has not been built -- there is no fallback path."""
-    global _lib
+    """Load the shared library (no compute) and bind every entry point from the library's own table of compiler-derived signatures.
+    Raises if it has not been built -- there is no fallback path."""
+    global _lib, EXPORTS, _SIGS, _ARG_CODES, MT_BLOCKS, PROF_INFO
     if _lib is None:
         if not os.path.isfile(_LIB_PATH):
             raise EngineError(f"{_LIB_PATH} is missing: run `python -m fullbatchtraining_amd.build` (needs hipcc). "
                               "The engine has no CPU or PyTorch fallback.")
         lib = C.CDLL(_LIB_PATH)
-        for name, sig in _SIGS.items():
-            fn = getattr(lib, name)
-            fn.argtypes, fn.restype = sig, c_int
-        lib.fb_last_error_string.restype = C.c_char_p
-        lib.fb_abi_version.restype = c_int
         if lib.fb_abi_version() != EXPECTED_ABI:           # a stale in-tree .so would read the argument structs with another layout
             raise EngineError(f"{_LIB_PATH} has ABI version {lib.fb_abi_version()}, this package expects {EXPECTED_ABI}: rebuild it with "
                               "`python -m fullbatchtraining_amd.build --force`")
-        lib.fb_ws_conv_stat_floats.argtypes, lib.fb_ws_conv_stat_floats.restype = [C.POINTER(ConvArgs)], c_i64
-        lib.fb_ws_wgrad_slab_floats.argtypes, lib.fb_ws_wgrad_slab_floats.restype = [C.POINTER(WgradArgs)], c_i64
-        lib.fb_ws_bn_partial_floats.argtypes, lib.fb_ws_bn_partial_floats.restype = [c_i64, c_int], c_i64
-        lib.fb_ws_mt_floats.argtypes, lib.fb_ws_mt_floats.restype = [c_int], c_i64
-        lib.fb_bn_bwd_reduce_rows.argtypes, lib.fb_bn_bwd_reduce_rows.restype = [c_i64, c_i64], c_int
-        lib.fb_conv_masked_addend_supported.argtypes, lib.fb_conv_masked_addend_supported.restype = [C.POINTER(ConvArgs)], c_int
-        lib.fb_conv_bwd_stat_supported.argtypes, lib.fb_conv_bwd_stat_supported.restype = [C.POINTER(ConvArgs)], c_int
-        lib.fb_ws_bn_amax_floats.argtypes, lib.fb_ws_bn_amax_floats.restype = [c_i64, c_int, c_i64], c_i64
-        lib.fb_bn_apply_can_pool.argtypes, lib.fb_bn_apply_can_pool.restype = [c_int, c_int, c_i64, c_int], c_int
-        lib.fb_bn_bwd_fused_supported.argtypes, lib.fb_bn_bwd_fused_supported.restype = [c_i64, c_int, c_i64, c_int], c_int
-        lib.fb_ws_bn_bwd_fused_floats.argtypes, lib.fb_ws_bn_bwd_fused_floats.restype = [c_i64, c_int, c_i64, c_int], c_i64
-        lib.fb_ws_bn_bwd_fused_ints.argtypes, lib.fb_ws_bn_bwd_fused_ints.restype = [c_i64], c_i64
-        lib.fb_wgrad_bn_fused_supported.argtypes, lib.fb_wgrad_bn_fused_supported.restype = [C.POINTER(WgradArgs)], c_int
-        lib.fb_wgrad_chain_supported.argtypes, lib.fb_wgrad_chain_supported.restype = [C.POINTER(WgradArgs)], c_int
-        lib.fb_cmd_fn_id.argtypes, lib.fb_cmd_fn_id.restype = [C.c_char_p], c_int
-        lib.fb_cmd_fn_nargs.argtypes, lib.fb_cmd_fn_nargs.restype = [c_int], c_int
-        lib.fb_event_new.argtypes, lib.fb_event_new.restype = [], c_int
-        lib.fb_event_count.argtypes, lib.fb_event_count.restype = [], c_int
-        lib.fb_event_record.argtypes, lib.fb_event_record.restype = [c_int, c_void_p], c_int
-        lib.fb_event_wait.argtypes, lib.fb_event_wait.restype = [c_int, c_void_p], c_int
-        lib.fb_cmdlist_create.argtypes, lib.fb_cmdlist_create.restype = [], c_void_p
-        lib.fb_cmdlist_destroy.argtypes, lib.fb_cmdlist_destroy.restype = [c_void_p], None
-        lib.fb_cmdlist_size.argtypes, lib.fb_cmdlist_size.restype = [c_void_p], c_i64
-        lib.fb_cmdlist_add_call.argtypes, lib.fb_cmdlist_add_call.restype = [c_void_p, c_int, C.POINTER(C.c_uint64), c_int, c_int, c_void_p, c_int], c_int
-        lib.fb_cmdlist_add_event.argtypes, lib.fb_cmdlist_add_event.restype = [c_void_p, c_int, c_int, c_int], c_int
-        lib.fb_cmdlist_replay.argtypes, lib.fb_cmdlist_replay.restype = [c_void_p, C.POINTER(c_void_p), c_int], c_int
+        lib.fb_entry_name.restype = lib.fb_entry_sig.restype = C.c_char_p      # (the getters of the table are in it too: rebound below)
+        exports, sigs, codes = [], {}, {}
+        for i in range(lib.fb_entry_count()):
+            name, sig = lib.fb_entry_name(i).decode(), lib.fb_entry_sig(i).decode()
+            fn, argtypes = getattr(lib, name), [_CTYPES[c] for c in sig[2:]]
+            fn.restype, fn.argtypes = _CTYPES[sig[0]], argtypes
+            exports.append(name)
+            if lib.fb_entry_kind(i) > 0:                   # a launch: ``call`` appends the stream
+                sigs[name], codes[name] = argtypes, sig[2:]
+        for which, cls in enumerate((ConvArgs, WgradArgs)):
+            check_layout(cls, _struct_fields(lib, which), lib.fb_struct_size(which))
+        if lib.fb_abi_constant(b"FB_PROF_CLASSES") != len(PROF_CLASSES):
+            raise EngineError(f"the library times {lib.fb_abi_constant(b'FB_PROF_CLASSES')} kernel classes, PROF_CLASSES names {len(PROF_CLASSES)}")
+        EXPORTS, _SIGS, _ARG_CODES = tuple(exports), sigs, codes
+        MT_BLOCKS, PROF_INFO = lib.fb_abi_constant(b"FB_MT_BLOCKS"), lib.fb_abi_constant(b"FB_PROF_INFO")
         _lib = lib
     return _lib
 
@@ -260,22 +216,23 @@ def event_wait(ev, stream=None):
 
 def _pack_words(name, args):
     """One 64-bit word per argument (the convention of fb_cmdlist_add_call) + the argument struct to copy, if the call has one."""
-    sig = _SIGS[name][:-1]
+    load()
+    sig = _ARG_CODES[name][:-1]
     if len(args) != len(sig):
         raise EngineError(f"{name}: {len(args)} arguments for a signature of {len(sig)}")
     words = (C.c_uint64 * len(sig))()
     blob = None
-    for i, (t, a) in enumerate(zip(sig, args)):
-        if t is c_float:
+    for i, (code, a) in enumerate(zip(sig, args)):
+        if code == "f":
             words[i] = struct.unpack("<I", struct.pack("<f", float(a)))[0]
-        elif t is c_double:
+        elif code == "d":
             words[i] = struct.unpack("<Q", struct.pack("<d", float(a)))[0]
-        elif t is c_void_p or t is c_int or t is c_i64:
+        elif code in "pil":
             words[i] = (0 if a is None else int(a)) & 0xFFFFFFFFFFFFFFFF
-        elif i == 0 and hasattr(a, "_obj"):              # C.byref(ConvArgs / WgradArgs): the executor keeps its own copy
+        elif i == 0 and code in "CW" and hasattr(a, "_obj"):      # C.byref(ConvArgs / WgradArgs): the executor keeps its own copy
             blob = a._obj
         else:
-            raise EngineError(f"{name}: argument {i} of type {t} cannot be recorded")
+            raise EngineError(f"{name}: argument {i} of type '{code}' cannot be recorded")
     return words, blob
 
 

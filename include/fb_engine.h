@@ -37,14 +37,35 @@ typedef enum { FB_F32 = 0, FB_BF16 = 1 } fb_dtype;
 const char* fb_last_error_string(void);
 int fb_abi_version(void);
 
+/* ---------------------------------------------------------------- the ABI, described by the library itself -------- */
+/* One table inside the library (csrc/cmdlist.cpp) lists every function declared in this header with its signature as the COMPILER sees
+ * it, so a host binding sets its argument types from the table instead of copying them by hand (ABI v15).
+ * fb_entry_sig(i): "<return>:<arguments>", one character each: v void, i 32-bit integer, l 64-bit integer, f float, d double, p any
+ * pointer, s const char*, C const fb_conv_args*, W const fb_wgrad_args*.  fb_entry_kind(i): 0 a host function (query, profiling, event,
+ * command list), 1 an asynchronous launch (returns a status, last argument the stream), 2 a launch that command lists can record
+ * (fb_cmd_fn_id).  Name and signature are NULL, the kind -1, for i outside [0, fb_entry_count()). */
+int32_t fb_entry_count(void);
+const char* fb_entry_name(int32_t i);
+const char* fb_entry_sig(int32_t i);
+int32_t fb_entry_kind(int32_t i);
+/* Layout of the argument structs, `which` 0: fb_conv_args, 1: fb_wgrad_args.  fb_struct_field returns the number of fields (FB_ERR_ARG
+ * for another `which`) and, for 0 <= i < that number, field i in declaration order: its name, byte offset, byte size and type code (as above). */
+int32_t fb_struct_field(int32_t which, int32_t i, const char** name, int32_t* offset, int32_t* size, char* code);
+int32_t fb_struct_size(int32_t which);           /* sizeof, -1 for an unknown struct */
+/* value of a constant of this header by name: "FB_MT_BLOCKS", "FB_PROF_CLASSES", "FB_PROF_INFO"; -1 for any other name */
+int32_t fb_abi_constant(const char* name);
+
 /* Optional measurement aid (the only process-global state in the library, off by default): while enabled every
  * fb_conv2d / fb_conv2d_wgrad launch is bracketed by HIP events recorded on the launch stream.  fb_profile_read waits
- * for the recorded launches and returns, per kernel class {0: igemm fwd, 1: igemm dgrad, 2: wgrad}, the summed
- * elapsed milliseconds, the number of launches and the number of launches that were not recorded (pool exhausted). */
+ * for the recorded launches and returns, per kernel class {0: igemm fwd, 1: igemm dgrad, 2: wgrad, 3: BN apply, 4: BN backward reduce,
+ * 5: BN backward apply, 6: fused BN backward}, the summed elapsed milliseconds, the number of launches and the number of launches that
+ * were not recorded (pool exhausted): three arrays of FB_PROF_CLASSES elements. */
+#define FB_PROF_CLASSES 7
+#define FB_PROF_INFO 11   /* shape words filed with a launch (fb_profile_read_launches) */
 int fb_profile_enable(int on, int capacity);
-int fb_profile_read(double* ms, int64_t* launches, int64_t* dropped);   /* arrays of 6: + {3: BN apply, 4: BN backward reduce, 5: BN backward apply} */
+int fb_profile_read(double* ms, int64_t* launches, int64_t* dropped);
 /* Per-launch records of everything recorded since the last fb_profile_read (which resets: call this one first).  Row i of `info`
- * ([cap][12] int32): {class, 11 shape words}: convolutions {n_img, Hs, Ws, Cs, Hd, Wd, Cd, R, stride, flags, kernel id}, BatchNorm passes
+ * ([cap][FB_PROF_INFO + 1] int32): {class, FB_PROF_INFO shape words}: convolutions {n_img, Hs, Ws, Cs, Hd, Wd, Cd, R, stride, flags, kernel id}, BatchNorm passes
  * {pixels/128, C, pixels_per_group/128, dtype, residual?, mask?, dy_out?, pooled?, 0, 0, 0}; ms[i] = elapsed milliseconds.
  * Returns the number of rows written (<= cap) or a negative fb_status. */
 int64_t fb_profile_read_launches(int32_t* info, float* ms, int64_t cap);

@@ -153,6 +153,133 @@ def test_command_list_host_side():
         h.fb_cmdlist_destroy(cl)
 
 
+def _header_declarations():
+    """{name: (signature in the codes of fb_entry_sig, text of the last parameter)} of every function ``include/fb_engine.h`` declares, read with
+    regular expressions only (no compiler): comments, preprocessor lines and typedef bodies go, every remaining statement must be a prototype."""
+    text = open(os.path.join(REPO, "include", "fb_engine.h")).read()
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M).replace('extern "C" {', " ")
+    text = re.sub(r"typedef\s+(?:struct|enum)\s*\{.*?\}\s*\w+\s*;", " ", text, flags=re.S)
+    pointers = {"const fb_conv_args *": "C", "const fb_wgrad_args *": "W", "const char *": "s"}
+    scalars = {"void": "v", "int": "i", "int32_t": "i", "int64_t": "l", "float": "f", "double": "d"}
+
+    def code(ctype):
+        ctype = " ".join(ctype.replace("*", " * ").split())
+        return pointers.get(ctype, "p") if ctype.endswith("*") else scalars[ctype]
+
+    out = {}
+    for statement in text.split(";"):
+        statement = " ".join(statement.split())
+        if statement in ("", "}"):
+            continue
+        m = re.fullmatch(r"(.+?)\b(fb_[a-z0-9_]+) ?\((.*)\)", statement)
+        assert m, statement
+        params = [] if m.group(3).strip() == "void" else [q.strip() for q in m.group(3).split(",")]
+        assert m.group(2) not in out, statement
+        out[m.group(2)] = (code(m.group(1)) + ":" + "".join(code(re.sub(r"\w+$", "", q)) for q in params), params[-1] if params else "")
+    return out
+
+
+def _entry_table(h):
+    return {h.fb_entry_name(i).decode(): (h.fb_entry_sig(i).decode(), h.fb_entry_kind(i)) for i in range(h.fb_entry_count())}
+
+
+def test_entry_table_has_the_signature_of_every_header_declaration():
+    """The library's table of compiler-derived signatures (what ``lib.load()`` binds from) against an independent reading of the header: the
+    same names, the same signature for each, and the ctypes attributes ``load()`` set are those signatures."""
+    from fullbatchtraining_amd import lib
+    h = lib.load()
+    declared = _header_declarations()
+    table = _entry_table(h)
+    assert len(declared) >= 78 and h.fb_entry_count() == len(table)                     # (no name twice)
+    assert set(table) == set(declared) and set(lib.EXPORTS) == set(declared) and len(lib.EXPORTS) == len(declared)
+    for name, (sig, _) in declared.items():
+        assert table[name][0] == sig, name
+        fn = getattr(h, name)
+        assert fn.restype is lib._CTYPES[sig[0]] and list(fn.argtypes) == [lib._CTYPES[c] for c in sig[2:]], name
+    assert declared["fb_bn_fwd_finalize"][0] == "i:piiidpplfppiipppp" and declared["fb_conv2d"][0] == "i:Cp"
+    assert declared["fb_ws_wgrad_slab_floats"][0] == "l:W" and declared["fb_last_error_string"][0] == "s:" and declared["fb_cmdlist_destroy"][0] == "v:p"
+    assert h.fb_entry_name(-1) is None and h.fb_entry_sig(h.fb_entry_count()) is None and h.fb_entry_kind(-1) == -1
+
+
+def test_entry_kinds_separate_launches_recordable_launches_and_host_functions():
+    """Launches (``lib._SIGS``: what ``lib.call`` may invoke and the confinement suite must cover) are exactly the functions that return int and end in
+    ``void* stream``, less the two eager event calls; the recordable ones are exactly those the command-list executor resolves."""
+    from fullbatchtraining_amd import lib
+    h = lib.load()
+    declared = _header_declarations()
+    table = _entry_table(h)
+    launches = {n for n, (sig, last) in declared.items() if sig.startswith("i:") and " ".join(last.replace("*", "* ").split()) == "void* stream"}
+    launches -= {"fb_event_record", "fb_event_wait"}
+    assert {n for n, (_, kind) in table.items() if kind > 0} == launches == set(lib._SIGS)
+    assert all(kind in (0, 1, 2) for _, kind in table.values())
+    recordable = {n for n, (_, kind) in table.items() if kind == 2}
+    assert recordable == {n for n in table if h.fb_cmd_fn_id(n.encode()) >= 0}
+    assert "fb_subsample2_fwd" in recordable and "fb_stem_patches" not in recordable and "fb_stem_patches" in launches
+    for n in recordable:
+        assert h.fb_cmd_fn_nargs(h.fb_cmd_fn_id(n.encode())) == len(table[n][0]) - 2 == len(lib._SIGS[n]), n
+    for n in set(table) - recordable:
+        assert h.fb_cmd_fn_id(n.encode()) == -1, n
+    assert h.fb_cmd_fn_id(b"fb_no_such_call") == -1 and h.fb_cmd_fn_nargs(-1) == -1 and h.fb_cmd_fn_nargs(h.fb_entry_count()) == -1
+
+
+def test_argument_structs_are_checked_against_the_library_layout():
+    """``lib.check_layout`` (run by ``load()`` on ConvArgs / WgradArgs) against the library's field tables: the shipped classes pass; a class with a
+    dropped field, two swapped fields, a narrowed integer or an extra trailing field is refused with that field named."""
+    import ctypes as C
+
+    from fullbatchtraining_amd import lib
+    h = lib.load()
+    for which, cls in enumerate((lib.ConvArgs, lib.WgradArgs)):
+        fields, size = lib._struct_fields(h, which), h.fb_struct_size(which)
+        assert [f[0] for f in fields] == [n for n, _ in cls._fields_] and size == C.sizeof(cls) and size % 8 == 0
+        lib.check_layout(cls, fields, size)
+    assert h.fb_struct_size(2) == -1 and h.fb_struct_field(2, 0, None, None, None, None) < 0
+
+    def refused(base, which, edit, named):
+        spec = list(base._fields_)
+        edit(spec)
+        variant = type("Variant", (C.Structure,), {"_fields_": spec})
+        with pytest.raises(lib.EngineError, match=rf"\b{named}\b"):
+            lib.check_layout(variant, lib._struct_fields(h, which), h.fb_struct_size(which))
+
+    def index(spec, name):
+        return [n for n, _ in spec].index(name)
+
+    def swap(spec, a, b):
+        i, j = index(spec, a), index(spec, b)
+        spec[i], spec[j] = spec[j], spec[i]
+
+    def retype(spec, name, ctype):
+        spec[index(spec, name)] = (name, ctype)
+
+    refused(lib.ConvArgs, 0, lambda spec: spec.pop(index(spec, "Hs")), "Hs")
+    refused(lib.ConvArgs, 0, lambda spec: swap(spec, "stride", "pad"), "stride")
+    refused(lib.ConvArgs, 0, lambda spec: swap(spec, "bst_x", "amax_src"), "bst_x")
+    refused(lib.ConvArgs, 0, lambda spec: retype(spec, "wset_stride", C.c_int32), "wset_stride")
+    refused(lib.ConvArgs, 0, lambda spec: retype(spec, "pad", C.c_float), "pad")                # (same size and offset, another type)
+    refused(lib.ConvArgs, 0, lambda spec: spec.append(("amax_extra", C.c_int32)), "amax_extra")   # (fits the tail padding: the size alone would not tell)
+    refused(lib.WgradArgs, 1, lambda spec: spec.pop(index(spec, "split_k")), "split_k")
+    refused(lib.WgradArgs, 1, lambda spec: retype(spec, "group_stride", C.c_int32), "group_stride")
+    refused(lib.WgradArgs, 1, lambda spec: spec.append(("bn_extra", C.c_void_p)), "bn_extra")
+    refused(lib.WgradArgs, 1, lambda spec: spec.pop(), "bn_coef")
+    # a field table that skips a field (a row forgotten in the library) does not pass either: the next field no longer follows its predecessor
+    fields = lib._struct_fields(h, 0)
+    with pytest.raises(lib.EngineError, match=r"\bHs\b"):
+        lib.check_layout(lib.ConvArgs, fields[:5] + fields[6:], h.fb_struct_size(0))
+
+
+def test_abi_constants_come_from_the_library():
+    from fullbatchtraining_amd import lib
+    h = lib.load()
+    assert h.fb_abi_constant(b"FB_MT_BLOCKS") == lib.MT_BLOCKS > 0 and h.fb_abi_constant(b"FB_PROF_INFO") == lib.PROF_INFO > 0
+    assert h.fb_abi_constant(b"FB_PROF_CLASSES") == len(lib.PROF_CLASSES)
+    assert h.fb_abi_constant(b"FB_NO_SUCH_CONSTANT") == -1 and h.fb_abi_constant(b"") == -1
+    header = open(os.path.join(REPO, "include", "fb_engine.h")).read()
+    for name in ("FB_MT_BLOCKS", "FB_PROF_CLASSES", "FB_PROF_INFO"):
+        assert int(re.search(rf"#define {name} (\d+)", header).group(1)) == h.fb_abi_constant(name.encode())
+
+
 def test_engine_fails_loudly_without_gpu():
     if torch.cuda.is_available():
         pytest.skip("GPU present")
