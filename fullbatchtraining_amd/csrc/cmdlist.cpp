@@ -97,6 +97,8 @@ constexpr Entry kEntries[] = {
     FB_RECORDABLE(fb_mt_norms2), FB_RECORDABLE(fb_mt_clip_sgd), FB_RECORDABLE(fb_mt_scale), FB_LAUNCH(fb_mt_sam_ascent), FB_LAUNCH(fb_mt_sam_restore),
     FB_LAUNCH(fb_mt_absmax2), FB_LAUNCH(fb_mt_pnorm2), FB_LAUNCH(fb_mt_norm_bias), FB_LAUNCH(fb_mt_ema), FB_LAUNCH(fb_mt_clip_scale),
     FB_LAUNCH(fb_mt_grad_noise),
+    // mini-batch SGD mode
+    FB_RECORDABLE(fb_mt_sgd_prep), FB_HOST(fb_mt_sgd_prep_supported), FB_RECORDABLE(fb_mt_sgd_torch),
 };
 constexpr int kNumEntries = sizeof(kEntries) / sizeof(kEntries[0]);
 constexpr bool launches_take_a_stream() {

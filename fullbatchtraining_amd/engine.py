@@ -1187,7 +1187,8 @@ class Engine:
 
     # --------------------------------------------------------------------------------------- full-batch gradient + step --
     def full_gradient(self, patches, labels, lr, block_strength=0.0, eps=1e-2, implementation="forward-differences",
-                      chunk_ids=None, counter0=0, acc_strength=0.0, after_pre_pass=None, pre_block=None, batch_clip=None, late_bucket=None):
+                      chunk_ids=None, counter0=0, acc_strength=0.0, after_pre_pass=None, pre_block=None, batch_clip=None, late_bucket=None,
+                      weights_prepared=False):
         """Accumulate the regularised gradient over chunks (reference training.py:144-174) into ``self.avg``.
 
         ``patches``/``labels`` hold the whole resident dataset; chunk k = rows [k*chunk, (k+1)*chunk).  ``chunk_ids``
@@ -1202,6 +1203,7 @@ class Engine:
         LAST chunk group has left the last stage, the slice [b, P) of the running mean (last stage + classifier, 3/4 of ResNet-18's
         parameters) is completed on a side stream and ``started()`` is called there (the caller starts that bucket's reduce-scatter);
         the slice [0, b) follows at the end as usual.
+        ``weights_prepared``: the shared compute-dtype weight copies already hold ``self.theta`` (``sgd_prep_step`` wrote them with the update).
         """
         chunk, P, G = self.chunk, self.plan.P, self.G
         n_chunks = patches.shape[0] // chunk if chunk_ids is None else len(chunk_ids)
@@ -1221,7 +1223,8 @@ class Engine:
                 raise lib.EngineError(f"Engine was built with fd_sets={self.fd_sets}; {implementation} needs {need}")
         if counter0 == 0:
             self.avg.zero_()
-        self.prep_weights(self.theta, 1)
+        if not weights_prepared:
+            self.prep_weights(self.theta, 1)
         pre = None
         if acc_strength != 0:
             # pre-pass (reference training.py:128-142): the plain full-batch gradient at theta, needed as a whole before the first
@@ -1389,6 +1392,36 @@ class Engine:
         call("fb_mt_clip_sgd", self.theta.data_ptr() + 4 * lo, self.avg.data_ptr() + 4 * lo, self.mom.data_ptr() + 4 * lo, n,
              self.norms2.data_ptr(), -1.0 if grad_clip is None else float(grad_clip), float(lr), float(weight_decay), float(momentum),
              float(dampening), 1 if nesterov else 0, 1 if self.first_step else 0)
+        self.first_step = False
+
+    def sgd_prep_fused(self):
+        """Whether the mini-batch update runs as ONE fb_mt_sgd_prep launch (update + both weight copies).  FB_SGD_FUSED=0 selects the
+        composition fb_mt_sgd_torch + fb_weight_prep per layer (same bits); the fp16x2 weight planes always take the composition."""
+        if os.environ.get("FB_SGD_FUSED", "1") == "0":
+            return False
+        return bool(lib.load().fb_mt_sgd_prep_supported(self.dtc, 1 if self.f32_split == "f16x2" else 0))
+
+    def sgd_layer_table(self):
+        """Device table of fb_mt_sgd_prep: one row {w_off, Cout, taps, Cin_real, Cin_pad, wc_off, has_dgrad, 0} per layer, sorted by w_off
+        (the stem has no transposed copy: nothing consumes its input gradient).  Built once: the library checks a table per address."""
+        if getattr(self, "_sgd_tab", None) is None:
+            rows = [[L.w_off, L.cout, L.taps, L.cin_real, L.cin_pad, L.wc_off, 0 if L is self.plan.stem else 1, 0]
+                    for L in sorted(self.plan.layers, key=lambda L: L.w_off)]
+            self._sgd_tab = torch.tensor(rows, dtype=torch.int32, device=self.device)
+        return self._sgd_tab
+
+    def sgd_prep_step(self, lr, weight_decay, momentum, dampening, nesterov, grad_clip=None, fused=True):
+        """The update of one mini-batch (reference training.py:274-281): ``torch.nn.utils.clip_grad_norm_`` -- coef = min(1, clip / (norm +
+        1e-6)) with |avg|^2 in ``self.norms2[0]`` -- then SGD on the whole arena; ``self.avg`` is left as it is.  ``fused``: the same launch
+        writes the shared weight copies of the new parameters (pass ``weights_prepared=True`` to the next ``full_gradient``)."""
+        args = (self.theta.data_ptr(), self.avg.data_ptr(), self.mom.data_ptr(), self.plan.P, self.norms2.data_ptr(),
+                -1.0 if grad_clip is None else float(grad_clip), float(lr), float(weight_decay), float(momentum), float(dampening),
+                1 if nesterov else 0, 1 if self.first_step else 0)
+        if fused:
+            tab = self.sgd_layer_table()
+            call("fb_mt_sgd_prep", *args, tab.data_ptr(), tab.shape[0], self.w_fwd[0].data_ptr(), self.w_dgrad[0].data_ptr(), self.dtc)
+        else:
+            call("fb_mt_sgd_torch", *args)
         self.first_step = False
 
     def sgd_step_per_tensor(self, lr, weight_decays, momentum, dampening, nesterov, grad_clip=None):

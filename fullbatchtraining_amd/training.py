@@ -288,10 +288,36 @@ def _stage(loader, device):
     return X.to(device), Y.to(device=device, dtype=torch.long)
 
 
-def _check_scope(cfg):
+def _check_scope(cfg, branch="full-batch"):
+    """Raises NotImplementedError unless ``cfg`` is in scope of ``branch`` of the reference's ``train()``: "full-batch" (training.py:224-239) or
+    "stochastic" (:241-286, the mini-batch SGD mode).  The trainer passes the branch ``hyp.train_stochastic`` selects; a caller that asks for the
+    full-batch branch -- the default, what this function has always meant -- with a configuration that selects the other one is refused."""
     hyp = cfg.hyp
-    if hyp.train_stochastic or hyp.train_switch_stochastic is not None:
-        raise NotImplementedError("the engine implements the full-batch branch (hyp.train_stochastic=False) only")
+    if branch not in ("full-batch", "stochastic"):
+        raise ValueError(f"branch {branch!r}: 'full-batch' or 'stochastic'")
+    if hyp.train_switch_stochastic is not None:
+        raise NotImplementedError("hyp.train_switch_stochastic: the reference never resets the flag it flips (training.py:222-223), so any value >= 0 "
+                                  "inverts hyp.train_stochastic for the whole run -- set hyp.train_stochastic itself")
+    if bool(hyp.train_stochastic) != (branch == "stochastic"):
+        raise NotImplementedError(f"hyp.train_stochastic={bool(hyp.train_stochastic)} does not select the {branch} branch this check was asked about "
+                                  "(FullBatchTrainer runs both: it checks the branch the configuration selects)")
+    if hyp.train_stochastic:         # mini-batch SGD mode (reference training.py:241-286)
+        if torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
+            raise NotImplementedError("hyp.train_stochastic on more than one rank (the reference all-reduces every mini-batch gradient; the engine's "
+                                      "mini-batch mode runs in one process)")
+        if hyp.optim_modification.name != "none":
+            raise NotImplementedError(f"hyp.train_stochastic with optim_modification {hyp.optim_modification.name!r} (the mini-batch update is plain "
+                                      "clip + SGD in one launch)")
+        if hyp.grad_reg.acc_strength != 0:
+            raise NotImplementedError("hyp.train_stochastic with grad_reg.acc_strength != 0 (the reference passes pre_grads=None to the regulariser, "
+                                      "training.py:265)")
+        if hyp.batch_clip is not None:
+            raise NotImplementedError("hyp.train_stochastic with hyp.batch_clip (the reference dies in _record_stats, training.py:117-118)")
+        if hyp.train_semi_stochastic:
+            raise NotImplementedError("hyp.train_semi_stochastic (needs the LMDB rounds of construct_subset_dataloader)")
+        if hyp.only_linear_layers_weight_decay:
+            raise NotImplementedError("hyp.train_stochastic with only_linear_layers_weight_decay (the mini-batch update takes one weight decay)")
+        return
     if hyp.grad_reg.acc_strength != 0 and max(cfg.data.batch_size // hyp.sub_batch, 1) != 1 \
             and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
         raise NotImplementedError("grad_reg.acc_strength with sub_batch < batch_size on several ranks (the pre-pass runs whole blocks; "
@@ -405,7 +431,7 @@ class FullBatchTrainer:
     """Owns the engine, the resident dataset and the optimizer/scheduler state containers for one training run."""
 
     def __init__(self, model, trainloader, validloader, setup, cfg):
-        _check_scope(cfg)
+        _check_scope(cfg, branch="stochastic" if cfg.hyp.train_stochastic else "full-batch")
         self.cfg, self.model = cfg, model
         self.device = torch.device(setup["device"]) if not isinstance(setup["device"], torch.device) else setup["device"]
         self.optimizer, self.scheduler = optim_interface(model, cfg.hyp)
@@ -426,7 +452,9 @@ class FullBatchTrainer:
         else:
             X, Y = _stage(trainloader, None)                         # only this rank's chunk range is copied to the device below
         block = min(cfg.data.batch_size, X.shape[0])
-        chunks_in_block = max(block // cfg.hyp.sub_batch, 1)
+        # mini-batch SGD mode: every block of the loader is ONE BatchNorm batch and one update (the stochastic branch has no sub_batch chunking)
+        self.stochastic = bool(cfg.hyp.train_stochastic)
+        chunks_in_block = 1 if self.stochastic else max(block // cfg.hyp.sub_batch, 1)
         if block % chunks_in_block != 0:
             raise NotImplementedError("data.batch_size must be divisible into equal sub_batch chunks")
         self.chunk, self.block = block // chunks_in_block, block
@@ -467,6 +495,8 @@ class FullBatchTrainer:
             log.warning(f"chunk group capped at {cap} chunks by the device's free memory (the nominal cap from its total memory is {cap_nominal}); "
                         "results are unchanged, launches are smaller")
         G = group_size(self.shard.count, want, cap=min(cap, cap_nominal))
+        if self.stochastic:                      # one block per gradient: the weights change before the next one
+            G = nominal = 1
         log.info(f"chunk groups: {G} chunks per launch on this rank ({self.shard.count} chunks), K-slice counts sized for a nominal group of {nominal}")
         self.engine = Engine(model, X.shape[-1], self.chunk_pad, G, compute_dtype=self.dtype, device=self.device, fd_sets=fd_sets,
                              arena_align=64 * self.world, chunk_valid=self.chunk, nominal_group=nominal,
@@ -489,6 +519,12 @@ class FullBatchTrainer:
             self._gather_patches(mine)
         del mine
         self.labels = self._pad_labels(Y[lo:hi].to(self.device)).clone()      # (a buffer of its own: a shuffling feed rewrites it every step)
+        if self.stochastic:
+            # ONE fixed staging buffer for the block in flight: the recorded launches of a chunk group are keyed by -- and hold -- the address of
+            # its patches, so one recorded list (two with the regulariser) serves every block of every epoch
+            self.stage_patches = torch.zeros(self.chunk_pad, *self.patches.shape[1:], device=self.device, dtype=self.dtype)
+            self.stage_labels = torch.full((self.chunk_pad,), -1, dtype=torch.long, device=self.device)
+            self.sgd_fused = self.engine.sgd_prep_fused()
         # a validation DataLoader is read once through a private loader (its generator untouched); every validation pass then advances
         # that generator by the one base-seed draw the reference's pass over it makes (keeps shared generators aligned)
         self._valid_loader = validloader if isinstance(validloader, torch.utils.data.DataLoader) else None
@@ -516,6 +552,8 @@ class FullBatchTrainer:
             self._regather_shuffled()
         lr = self.optimizer.param_groups[0]["lr"]
         gr = hyp.grad_reg
+        if self.stochastic:
+            return self._sgd_epoch(lr, train_time)
         if self.multi:
             self._running0 = torch.stack([eng.running_mean, eng.running_var]).clone()
         mod = hyp.optim_modification.name
@@ -614,6 +652,45 @@ class FullBatchTrainer:
             self.scheduler.step()
             return
         self._record_stats(loss_k, correct_k, sq_k, eng.norms2, lr, train_time)
+        self.scheduler.step()
+
+    def _sgd_epoch(self, lr, train_time):
+        """One "step" of the stochastic branch = one epoch (reference training.py:241-286): per block of the loader the block gradient as one
+        BatchNorm batch (|g|^2 of the raw gradient, then the regulariser with the epoch's lr), ``clip_grad_norm_`` (always L2, the torch form),
+        the SGD update; ``_modify_gradient_params`` is commented out there, so there is no norm bias, no gradient noise and no
+        preclip_gradnorm / clipped_step.  Nothing here waits for the device: losses, hits and norms of the blocks land in device arrays that
+        ``_record_stats`` reads back once."""
+        eng, hyp, o, gr = self.engine, self.cfg.hyp, self.cfg.hyp.optim, self.cfg.hyp.grad_reg
+        nb, cp = self.num_blocks, self.chunk_pad
+        f32 = dict(device=self.device, dtype=torch.float32)
+        loss_all, correct_all, sq_all = torch.empty(nb, **f32), torch.empty(nb, **f32), torch.empty(nb, **f32)
+        # tools/sgd_mode_bench.py: a list here collects one (begin, end) device-event pair per block around the update section
+        sections = getattr(self, "sgd_section_events", None)
+        for b in range(nb):
+            self.stage_patches.copy_(self.patches[b * cp:(b + 1) * cp])
+            self.stage_labels.copy_(self.labels[b * cp:(b + 1) * cp])
+            # (the first block of an epoch prepares the copies itself: evaluation, an EMA swap or a checkpoint load may have come between)
+            loss_k, correct_k, sq_k = eng.full_gradient(self.stage_patches, self.stage_labels, lr, gr.block_strength, gr.eps, gr.implementation,
+                                                        weights_prepared=b > 0)
+            loss_all[b:b + 1].copy_(loss_k)
+            correct_all[b:b + 1].copy_(correct_k)
+            sq_all[b:b + 1].copy_(sq_k)
+            if sections is not None:
+                begin = torch.cuda.Event(enable_timing=True)
+                begin.record()
+            # ---- the update section: norm, update, compute-dtype copies of the new parameters
+            if hyp.grad_clip is not None:        # |avg|^2 of the (regularised) block gradient for the clip
+                lib.call("fb_mt_norms2", eng.avg.data_ptr(), None, eng.plan.P, eng.norms2.data_ptr(), eng.mt_ws.data_ptr())
+            eng.sgd_prep_step(lr, o.weight_decay, o.momentum, o.dampening, o.nesterov, hyp.grad_clip, fused=self.sgd_fused)
+            if not self.sgd_fused:               # the composition: fb_weight_prep per layer (a recorded list)
+                eng.prep_weights(eng.theta, 1)
+            if sections is not None:
+                end = torch.cuda.Event(enable_timing=True)
+                end.record()
+                sections.append((begin, end))
+        self._pre_sqnorm = None
+        norms = eng.grad_and_param_sqnorm()      # param_norm: the parameters after the last update (reference training.py:92)
+        self._record_stats(loss_all, correct_all, sq_all, norms, lr, train_time)
         self.scheduler.step()
 
     def _gather_patches(self, images, aug=None):
@@ -744,7 +821,7 @@ class FullBatchTrainer:
         stats.raw("full_loss").append(full_loss.item())
         if hyp.batch_clip is not None:
             stats.raw("clipped_batches").append(int(clipped.item()))
-        if hyp.grad_clip is not None:
+        if hyp.grad_clip is not None and not self.stochastic:      # (recorded by _modify_gradient_params, which the stochastic branch does not call)
             grad_norm = gn2.sqrt().item()
             stats.raw("preclip_gradnorm").append(grad_norm)
             stats.raw("clipped_step").append(1 if grad_norm > hyp.grad_clip else 0)
@@ -902,6 +979,11 @@ def train(model, trainloader, validloader, setup, cfg):
         if cfg.dryrun:
             break
     trainer.gather_state()
-    eng.store_to_model(model, with_grad=True)    # closure contract: p.grad holds the last (clipped) full gradient
+    eng.store_to_model(model, with_grad=not trainer.stochastic)    # closure contract: p.grad holds the last (clipped) full gradient
+    if trainer.stochastic:                       # ... while the stochastic branch ends every update with optimizer.zero_grad() (training.py:282)
+        import inspect
+        to_none = inspect.signature(torch.optim.Optimizer.zero_grad).parameters["set_to_none"].default
+        for p in model.parameters():
+            p.grad = None if to_none else torch.zeros_like(p)
     _sync_optimizer_state(eng, model, optimizer)
     return stats

@@ -376,6 +376,21 @@ int fb_mt_ema(float* ema, const float* src, int64_t n, float momentum, float one
  *   fb_mt_grad_noise : mode 0: grad += strength * noise ; mode 1: grad *= 1 + strength * noise   (noise drawn by the caller) */
 int fb_mt_clip_scale(float* grad, int64_t n, const float* gnorm2, float grad_clip, void* stream);
 int fb_mt_grad_noise(float* grad, const float* noise, int64_t n, float strength, int32_t mode, void* stream);
+/* Mini-batch SGD mode (hyp.train_stochastic, reference training.py:241-286; ABI v16).  One pass over the arena [0, n) that turns
+ * (theta, grad, mom) into (theta', mom') -- the clip of torch.nn.utils.clip_grad_norm_, coef = min(1, grad_clip / (sqrt(gnorm2[0]) + 1e-6))
+ * (grad_clip < 0: none), then the arithmetic of fb_mt_clip_sgd; grad is read only -- AND writes the compute-dtype copies of theta' that
+ * fb_weight_prep would: forward [co][tap][ci_pad] into w_fwd, transposed [ci][tap][co] into w_dgrad (element offsets wc_off; padding
+ * columns Cin_real <= ci < Cin_pad are neither read nor written).  layer_tab: DEVICE array [n_layers][8] sorted by w_off,
+ * {w_off, Cout, taps, Cin_real, Cin_pad, wc_off, has_dgrad, 0}; elements outside every layer get the update only.  dtype FB_F32 / FB_BF16
+ * (fb_mt_sgd_prep_supported(dtype, f16x2_planes) == 0: compose fb_mt_sgd_torch + fb_weight_prep instead).  The host checks the table once
+ * per (address, n_layers) -- one blocking read-back on first sight -- and refuses an unsorted or out-of-range one without a launch.
+ *   fb_mt_sgd_torch: the update alone, same clip form and the same bits for theta' / mom'. */
+int fb_mt_sgd_prep(float* theta, const float* grad, float* mom, int64_t n, const float* gnorm2, float grad_clip, float lr,
+                   float weight_decay, float momentum, float dampening, int32_t nesterov, int32_t first_step, const int32_t* layer_tab,
+                   int32_t n_layers, void* w_fwd, void* w_dgrad, int32_t dtype, void* stream);
+int32_t fb_mt_sgd_prep_supported(int32_t dtype, int32_t f16x2_planes);
+int fb_mt_sgd_torch(float* theta, const float* grad, float* mom, int64_t n, const float* gnorm2, float grad_clip, float lr,
+                    float weight_decay, float momentum, float dampening, int32_t nesterov, int32_t first_step, void* stream);
 
 #ifdef __cplusplus
 }
