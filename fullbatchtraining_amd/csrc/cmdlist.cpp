@@ -79,21 +79,19 @@ constexpr Entry kEntries[] = {
     FB_HOST(fb_cmdlist_add_event), FB_HOST(fb_cmdlist_replay),
     // convolution
     FB_RECORDABLE(fb_conv2d), FB_HOST(fb_conv_masked_addend_supported), FB_HOST(fb_conv_bwd_stat_supported), FB_RECORDABLE(fb_absmax),
-    FB_HOST(fb_wgrad_bn_fused_supported), FB_RECORDABLE(fb_conv2d_wgrad), FB_HOST(fb_wgrad_chain_supported), FB_RECORDABLE(fb_conv2d_wgrad_chain),
+    FB_HOST(fb_wgrad_bn_fused_supported), FB_RECORDABLE(fb_conv2d_wgrad),
     FB_HOST(fb_ws_conv_stat_floats), FB_HOST(fb_ws_wgrad_slab_floats), FB_HOST(fb_ws_bn_partial_floats), FB_HOST(fb_ws_mt_floats),
     FB_RECORDABLE(fb_wgrad_reduce), FB_RECORDABLE(fb_weight_prep),
     // batch norm
     FB_RECORDABLE(fb_bn_fwd_finalize), FB_RECORDABLE(fb_bn_apply), FB_HOST(fb_ws_bn_amax_floats), FB_HOST(fb_bn_apply_can_pool),
     FB_RECORDABLE(fb_bn_running_update), FB_HOST(fb_bn_bwd_reduce_rows), FB_RECORDABLE(fb_bn_bwd_reduce), FB_RECORDABLE(fb_bn_bwd_finalize),
-    FB_RECORDABLE(fb_bn_bwd_apply), FB_RECORDABLE(fb_bn_bwd_reduce2), FB_RECORDABLE(fb_bn_bwd_apply2), FB_HOST(fb_bn_bwd_fused_supported),
-    FB_HOST(fb_ws_bn_bwd_fused_floats), FB_HOST(fb_ws_bn_bwd_fused_ints), FB_RECORDABLE(fb_bn_bwd_fused),
+    FB_RECORDABLE(fb_bn_bwd_apply), FB_RECORDABLE(fb_bn_bwd_reduce2), FB_RECORDABLE(fb_bn_bwd_apply2),
     // data path (fb_stem_patches takes a HOST array), pooling, head
     FB_LAUNCH(fb_stem_patches), FB_RECORDABLE(fb_avgpool2_fwd), FB_RECORDABLE(fb_subsample2_fwd), FB_RECORDABLE(fb_subsample2_bwd_add),
     FB_RECORDABLE(fb_maxpool3s2_fwd), FB_RECORDABLE(fb_maxpool3s2_bwd), FB_RECORDABLE(fb_maxpool3s2_fwd_idx), FB_RECORDABLE(fb_maxpool3s2_bwd_idx),
     FB_RECORDABLE(fb_head_pool), FB_RECORDABLE(fb_head_loss), FB_RECORDABLE(fb_bn_eval_coeffs), FB_LAUNCH(fb_head_tta), FB_RECORDABLE(fb_head_bwd),
     // multi-tensor
-    FB_RECORDABLE(fb_mt_sqnorm), FB_RECORDABLE(fb_mt_accumulate), FB_RECORDABLE(fb_mt_accumulate_sum), FB_RECORDABLE(fb_mt_accumulate_skip),
-    FB_RECORDABLE(fb_mt_fd_perturb), FB_RECORDABLE(fb_mt_fd_combine_accumulate), FB_RECORDABLE(fb_mt_fd_combine), FB_RECORDABLE(fb_mt_chunk_clip),
+    FB_RECORDABLE(fb_mt_sqnorm), FB_RECORDABLE(fb_mt_accumulate), FB_RECORDABLE(fb_mt_fd_perturb), FB_RECORDABLE(fb_mt_fd_combine_accumulate), FB_RECORDABLE(fb_mt_fd_combine), FB_RECORDABLE(fb_mt_chunk_clip),
     FB_RECORDABLE(fb_mt_norms2), FB_RECORDABLE(fb_mt_clip_sgd), FB_RECORDABLE(fb_mt_scale), FB_LAUNCH(fb_mt_sam_ascent), FB_LAUNCH(fb_mt_sam_restore),
     FB_LAUNCH(fb_mt_absmax2), FB_LAUNCH(fb_mt_pnorm2), FB_LAUNCH(fb_mt_norm_bias), FB_LAUNCH(fb_mt_ema), FB_LAUNCH(fb_mt_clip_scale),
     FB_LAUNCH(fb_mt_grad_noise),

@@ -343,7 +343,7 @@ __device__ __forceinline__ void store_b128_guard(fb_store_u32x4 data) {
 }
 
 // dx of a BatchNorm backward, dx = c_dy * dy + c_x * x + c_0 (coefficients from fb_bn_bwd_finalize): ONE spelling with explicit fused multiply-adds,
-// shared by every kernel that evaluates it (fb_bn_bwd_apply / _apply2, the stem weight gradient's loader, fb_bn_bwd_fused) -- left to the
+// shared by every kernel that evaluates it (fb_bn_bwd_apply / _apply2, the stem weight gradient's loader) -- left to the
 // compiler's contraction the same source line rounded differently in two instantiations of one template (fp32, last bit)
 __device__ __forceinline__ float fb_bn_dx(float c_dy, float c_x, float c_0, float dy, float x) { return fmaf(c_dy, dy, fmaf(c_x, x, c_0)); }
 

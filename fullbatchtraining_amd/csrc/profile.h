@@ -4,9 +4,8 @@
 #include <stdint.h>
 
 #include "../../include/fb_engine.h"   // FB_PROF_CLASSES, FB_PROF_INFO
-enum { FB_PROF_IGEMM_FWD = 0, FB_PROF_IGEMM_DGRAD = 1, FB_PROF_WGRAD = 2, FB_PROF_BN_APPLY = 3, FB_PROF_BN_BWD_REDUCE = 4, FB_PROF_BN_BWD_APPLY = 5,
-       FB_PROF_BN_BWD_FUSED = 6 };
-static_assert(FB_PROF_BN_BWD_FUSED + 1 == FB_PROF_CLASSES, "fb_engine.h: FB_PROF_CLASSES counts the classes above");
+enum { FB_PROF_IGEMM_FWD = 0, FB_PROF_IGEMM_DGRAD = 1, FB_PROF_WGRAD = 2, FB_PROF_BN_APPLY = 3, FB_PROF_BN_BWD_REDUCE = 4, FB_PROF_BN_BWD_APPLY = 5 };
+static_assert(FB_PROF_BN_BWD_APPLY + 1 == FB_PROF_CLASSES, "fb_engine.h: FB_PROF_CLASSES counts the classes above");
 // the FB_PROF_INFO shape words filed with a launch (fb_profile_read_launches): convolutions {n_img, Hs, Ws, Cs, Hd, Wd, Cd, R, stride, flags, kernel};
 // BatchNorm passes {pixels / 128, C, pixels_per_group / 128, dtype, residual?, mask?, dy_out?, pooled?, 0, 0, kernel}
 // which kernel served a convolution launch (last shape word)

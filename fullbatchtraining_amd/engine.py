@@ -366,15 +366,6 @@ class Engine:
         self.fuse_bwd_stat = exp and os.environ.get("FB_FUSED_BWD_STAT", "0") != "0"     # BN-backward reduction in the input-gradient epilogues: built, parity-tested,
         # measured SLOWER at step level (profiles/r2_notes.md: the separate HBM-bound reduction overlaps the weight-gradient stream) -> off
         self.bst_done = False
-        # BatchNorm backward in one pass over (dout, x) with a chunk's operands held in registers by a resident cluster of workgroups
-        # (csrc/bn_bwd_fused.hip): built, parity-tested, and measured SLOWER than reduce -> finalize -> apply (2.1 vs 1.27 ms on the 64-channel layer:
-        # eight waves per CU pulling 128 KiB bursts reach 2.8 TB/s even without the waits -- profiles/r4_notes.md) -> off; FB_BN_BWD_FUSED=1 selects it
-        self.bn_fused = exp and os.environ.get("FB_BN_BWD_FUSED", "0") == "1"
-        # partial rows: (vectors of the tensor / 4096) x 2C floats, whatever the grouping -- sized for the largest layer of a full group
-        es = torch.empty((), dtype=self.dt).element_size()
-        self.bnf_ws = torch.empty(max((self.G * chunk * L.hout * L.wout * L.cout * es // 16 // 4096 * 2 + 4 * self.G) * L.cout for L in self.plan.layers) + 64,
-                                  device=self.device, dtype=torch.float32)
-        self.bnf_sync = torch.zeros(int(lib.load().fb_ws_bn_bwd_fused_ints(self.G)), device=self.device, dtype=torch.int32)
         # weight gradients depend on nothing downstream in the backward chain: they run on their own stream, overlapping the
         # HBM-bound BN backward kernels and the dgrad convolutions of the main stream (FB_WGRAD_STREAM=0: same stream)
         sw = os.environ.get("FB_WGRAD_STREAM")
@@ -422,39 +413,6 @@ class Engine:
                 n_img=n, imgs_per_group=self.chunk, split_k=L.split_k, Cd=L.cout, R=L.R, S=L.S, Cs=L.cin_pad))))
         self.stat_ws = torch.empty(max_part, **f32)
         self.slab_ws = torch.empty(max_slab, **f32)
-        # Chunk-chained weight gradients (fb_conv2d_wgrad_chain; full_gradient's plain bf16 path): for the 3x3 layers on 4x4 maps -- 7 of the 11 M
-        # parameters of ResNet-18 -- the kernel leaves the SUM of the group's chunk gradients in ``gsum`` and every chunk's sum of squares in
-        # ``L.chain_sq`` instead of one fp32 gradient per chunk in the arena (2.8 GB per group written there and read again by the running mean).
-        self.chain_layers, self.chain_on = [], False
-        # OPT-IN (FB_WGRAD_CHAIN=1): the running-mean pass drops from 4.0 to 1.7 ms/step, but the chained kernel -- one 8-wave workgroup per CU with
-        # two accumulator sets -- takes 840 us where the per-chunk kernel with two independent 4-wave workgroups takes 692 (profiles/r4_notes.md)
-        if dt == torch.bfloat16 and os.environ.get("FB_WGRAD_CHAIN", "0") == "1" and os.environ.get("FB_EXPERIMENTAL", "0") not in ("", "0"):
-            for L in self.plan.layers:
-                a = lib.WgradArgs(None, None, None, n, L.hin, L.win, L.cin_pad, L.hout, L.wout, L.cout, L.R, L.S, L.stride, L.pad, self.chunk, 1, self.dtc, 0)
-                # (at most four: fb_mt_accumulate_skip leaves four ranges of the arena alone)
-                if (len(self.chain_layers) < 4 and L.split_k == 1 and L.cin_pad == L.cin_real and L.w_off % 4 == 0
-                        and bool(lib.load().fb_wgrad_chain_supported(lib.C.byref(a)))):
-                    L.chain_tiles = (L.cout // 64) * (L.cin_pad // 64)
-                    # one 8-wave workgroup per CU and chain; FB_WGRAD_CHAINS overrides the number of chains per tile
-                    L.n_chains = int(os.environ.get("FB_WGRAD_CHAINS", "0")) or max(1, 512 // L.chain_tiles)
-                    L.chain_sq = torch.zeros(self.G, L.chain_tiles * 8, **f32)
-                    self.chain_layers.append(L)
-        if self.chain_layers:
-            self.chain_ws = torch.empty(max(min(L.n_chains, self.G) * L.cout * L.taps * L.cin_pad for L in self.chain_layers), **f32)
-            self.gsum = torch.zeros(self.plan.P, **f32)
-            # the arena ranges that stay per chunk: [0, P) minus the chained layers' weights
-            cuts, lo = [], 0
-            for L in sorted(self.chain_layers, key=lambda l: l.w_off):
-                if L.w_off > lo:
-                    cuts.append((lo, L.w_off))
-                lo = L.w_off + L.cout * L.taps * L.cin_real
-            if lo < self.plan.P:
-                cuts.append((lo, self.plan.P))
-            assert all(a % 4 == 0 for a, _ in cuts), cuts
-            self.plain_segments = cuts
-            # scratch rows for the per-chunk norms of the non-chained ranges: one per caller of _fold that may be in flight at the same time
-            # (row 0: the main / weight-gradient stream, row 1: the side stream of the multi-GPU late bucket)
-            self.sq_seg = torch.zeros(2, self.G, **f32)
         self.stem_out = torch.empty(n, self.plan.stem.hout, self.plan.stem.wout, 64, device=dev, dtype=dt)
         if self.plan.stem_pool:
             hp = (self.plan.stem.hout + 1) // 2
@@ -807,16 +765,6 @@ class Engine:
         y = None if bits is not None else mask
         dx = self.pool.get((n, L.hout, L.wout, L.cout)) if apply else None
         dy = self.pool.get((n, L.hout, L.wout, L.cout)) if want_dy else None
-        if (apply and not reduced and y is None and self.bn_fused and self.f32_split != "f16x2"
-                and lib.load().fb_bn_bwd_fused_supported(px, L.cout, ppg, self.dtc)):
-            # one pass over (dout, x): a resident cluster of workgroups holds a chunk's operands in registers between the reduction and the
-            # apply step (csrc/bn_bwd_fused.hip) -- 3 tensor passes instead of the 5 of reduce -> finalize -> apply below
-            if int(lib.load().fb_ws_bn_bwd_fused_floats(px, L.cout, ppg, self.dtc)) > self.bnf_ws.numel():
-                raise lib.EngineError("fb_bn_bwd_fused: partial-row scratch too small for this launch")
-            call("fb_bn_bwd_fused", dout.data_ptr(), _ptr(bits), L.x.data_ptr(), self.mean_tab[pidx].data_ptr(), L.invstd.data_ptr(), L.scale.data_ptr(),
-                 self.plan.ch_total, L.ch_off, gout.data_ptr() + 4 * L.g_off, gout.data_ptr() + 4 * L.b_off, self.plan.P, L.coef.data_ptr(),
-                 dx.data_ptr(), _ptr(dy), px, L.cout, ppg, float(self.valid * L.hout * L.wout), self.dtc, self.bnf_ws.data_ptr(), self.bnf_sync.data_ptr())
-            return dx, dy
         if reduced:
             n_mblocks = px // 128
         else:
@@ -875,25 +823,6 @@ class Engine:
         n = G * self.chunk
         if bn is not None:
             dx = bn[0]
-        if self.chain_on and bn is None and any(L is c for c in self.chain_layers):
-            # the group's SUM into gsum[w_off:] + the chunks' sums of squares into L.chain_sq (no arena rows for this layer)
-            S = min(L.n_chains, G)
-            a = lib.WgradArgs(src.data_ptr(), dx.data_ptr(), None, n, L.hin, L.win, L.cin_pad, L.hout, L.wout, L.cout, L.R, L.S, L.stride, L.pad,
-                              self.chunk, 1, self.dtc, 0)
-
-            def launch_chain():
-                call("fb_conv2d_wgrad_chain", lib.C.byref(a), S, self.chain_ws.data_ptr(), L.chain_sq.data_ptr())
-                call("fb_wgrad_reduce", self.chain_ws.data_ptr(), self.gsum.data_ptr() + 4 * L.w_off, 0, 1, S, L.cout, L.taps, L.cin_pad, L.cin_real)
-
-            if self.wstream is None:
-                launch_chain()
-                return
-            ready = self.events.record()
-            with torch.cuda.stream(self.wstream):
-                self.events.wait(ready)
-                launch_chain()
-                self._wgrad_event = self.events.record()
-            return
         # one K slice and no channel padding: the kernel writes the per-chunk gradients straight into the arena rows
         direct = L.split_k == 1 and L.cin_pad == L.cin_real
         am_x = am_dy = None
@@ -1120,7 +1049,7 @@ class Engine:
         if on_block_done is not None or getattr(self, "_eval", False):
             return body()                            # (a host callback inside the sequence: the multi-GPU late bucket)
         self._replayable(("group", patches.data_ptr(), labels.data_ptr(), G, gout.data_ptr(), wsets, theta.data_ptr(), pidx, self.chunk, self.valid,
-                          float(self.label_smoothing), bool(self.only_incorrect), self.fuse_bwd_stat, self.chain_on), body)
+                          float(self.label_smoothing), bool(self.only_incorrect), self.fuse_bwd_stat), body)
 
     def choose_schedule(self, patches, labels, n_chunks):
         """The stream choice of a wide Bottleneck net NOW, if it is still pending (otherwise the first full_gradient call makes it): a caller that times its first
@@ -1156,34 +1085,6 @@ class Engine:
             times = {"two": float(t[0]), "one": float(t[1])}
         self.stream_times = times
         self.wstream = None if times["one"] < 0.995 * times["two"] else two
-
-    def _fold(self, gbuf, g_n, lo, hi, counter, sq_out, ws, seg_row=0):
-        """The running mean over [lo, hi) of the arena advanced by the ``g_n`` chunks in ``gbuf`` (+ their squared norms over that range into
-        ``sq_out[:g_n]``): fb_mt_accumulate; with chained weight gradients the chained layers from their group sum (fb_mt_accumulate_sum), the
-        rest per chunk with those ranges left alone (fb_mt_accumulate_skip), the norms as the sum of the two kinds of parts.  ``seg_row``: the
-        caller's own row of ``self.sq_seg`` (two folds of one step run on different streams with no order between them: the late bucket's on the
-        side stream, the early range's on the main stream -- each needs scratch of its own)."""
-        P = self.plan.P
-        if not self.chain_on:
-            call("fb_mt_accumulate", self.avg.data_ptr() + 4 * lo, gbuf.data_ptr() + 4 * lo, P, g_n, hi - lo, counter, _ptr(sq_out), ws.data_ptr())
-            return
-        parts, skips = [], []
-        for L in self.chain_layers:
-            size = L.cout * L.taps * L.cin_real
-            if lo <= L.w_off and L.w_off + size <= hi:
-                call("fb_mt_accumulate_sum", self.avg.data_ptr() + 4 * L.w_off, self.gsum.data_ptr() + 4 * L.w_off, size, counter, g_n)
-                parts.append(L.chain_sq[:g_n].sum(1))
-                skips += [L.w_off - lo, L.w_off - lo + size]
-            elif L.w_off < hi and L.w_off + size > lo:
-                raise lib.EngineError("a chained layer straddles the bucket boundary")
-        if len(skips) > 8:
-            raise lib.EngineError("more than four chained layers in one range")
-        skips += [0] * (8 - len(skips))
-        call("fb_mt_accumulate_skip", self.avg.data_ptr() + 4 * lo, gbuf.data_ptr() + 4 * lo, P, g_n, hi - lo, counter,
-             self.sq_seg[seg_row].data_ptr() if sq_out is not None else None, ws.data_ptr(), *skips)
-        parts.append(self.sq_seg[seg_row, :g_n])
-        if sq_out is not None:
-            sq_out[:g_n].copy_(torch.stack(parts).sum(0))
 
     # --------------------------------------------------------------------------------------- full-batch gradient + step --
     def full_gradient(self, patches, labels, lr, block_strength=0.0, eps=1e-2, implementation="forward-differences",
@@ -1273,113 +1174,104 @@ class Engine:
         if overlap and getattr(self, "g_alt", None) is None:
             self.g_alt, self.acc_ws = torch.zeros_like(self.g), torch.zeros_like(self.mt_ws)
         done, group_idx = 0, 0
-        # chained weight gradients: only where nothing needs a chunk's gradient itself (no regulariser, no per-chunk clip)
-        self.chain_on = bool(self.chain_layers) and not fd and batch_clip is None
         if late_bucket is not None and getattr(self, "side", None) is None:
             self.side = torch.cuda.Stream(device=self.device)
             self.sq_late, self.ws_late = torch.zeros_like(self.sq), torch.zeros_like(self.mt_ws)
-        try:
-            while done < n_chunks:
-                g_n = min(G, n_chunks - done)
-                lo = (k_first + done) * chunk
-                xb, yb = patches[lo:lo + g_n * chunk], labels[lo:lo + g_n * chunk]
-                gbuf = self.g_alt if (overlap and group_idx & 1) else self.g
-                group_idx += 1
-                # early completion of the late bucket: only for the last group, and only where the running mean is folded in one piece
-                early = late_bucket is not None and done + g_n == n_chunks and not overlap and batch_clip is None
-                lb = late_bucket[0] if early else 0
-                central = fd and implementation == "central-differences"
-                legacy = fd and implementation == "forward-differences-legacy"
-                cf = (lr / 4 * (block_strength if legacy else 1.0)) if fd else 0.0
+        while done < n_chunks:
+            g_n = min(G, n_chunks - done)
+            lo = (k_first + done) * chunk
+            xb, yb = patches[lo:lo + g_n * chunk], labels[lo:lo + g_n * chunk]
+            gbuf = self.g_alt if (overlap and group_idx & 1) else self.g
+            group_idx += 1
+            # early completion of the late bucket: only for the last group, and only where the running mean is folded in one piece
+            early = late_bucket is not None and done + g_n == n_chunks and not overlap and batch_clip is None
+            lb = late_bucket[0] if early else 0
+            central = fd and implementation == "central-differences"
+            legacy = fd and implementation == "forward-differences-legacy"
+            cf = (lr / 4 * (block_strength if legacy else 1.0)) if fd else 0.0
 
-                def finish_late(bi, _g_n=g_n, _done=done):
-                    """Called by the last backward pass of the group: gradients of the arena slice [lb, P) are complete."""
-                    if bi != self.plan.late_block:
-                        return
-                    ready = [torch.cuda.current_stream().record_event()]
-                    if self.wstream is not None:
-                        ready.append(self.wstream.record_event())
-                    with torch.cuda.stream(self.side):
-                        for ev in ready:
-                            self.side.wait_event(ev)
-                        n_late = P - lb
-                        if not fd:
-                            self._fold(self.g, _g_n, lb, P, counter0 + _done, self.sq_late, self.ws_late, seg_row=1)
-                        else:
-                            gb = self.g_fd[1] if central else self.g
-                            call("fb_mt_fd_combine_accumulate", self.avg.data_ptr() + 4 * lb, self.g.data_ptr() + 4 * lb, self.g_fd[0].data_ptr() + 4 * lb,
-                                 gb.data_ptr() + 4 * lb, P, _g_n, n_late, self.eps_n.data_ptr(), cf, counter0 + _done)
-                        late_bucket[1]()
+            def finish_late(bi, _g_n=g_n, _done=done):
+                """Called by the last backward pass of the group: gradients of the arena slice [lb, P) are complete."""
+                if bi != self.plan.late_block:
+                    return
+                ready = [torch.cuda.current_stream().record_event()]
+                if self.wstream is not None:
+                    ready.append(self.wstream.record_event())
+                with torch.cuda.stream(self.side):
+                    for ev in ready:
+                        self.side.wait_event(ev)
+                    n_late = P - lb
+                    if not fd:
+                        call("fb_mt_accumulate", self.avg.data_ptr() + 4 * lb, self.g.data_ptr() + 4 * lb, P, _g_n, n_late, counter0 + _done,
+                             self.sq_late.data_ptr(), self.ws_late.data_ptr())
+                    else:
+                        gb = self.g_fd[1] if central else self.g
+                        call("fb_mt_fd_combine_accumulate", self.avg.data_ptr() + 4 * lb, self.g.data_ptr() + 4 * lb, self.g_fd[0].data_ptr() + 4 * lb,
+                             gb.data_ptr() + 4 * lb, P, _g_n, n_late, self.eps_n.data_ptr(), cf, counter0 + _done)
+                    late_bucket[1]()
 
-                hook = finish_late if early else None
-                self.group_gradient(xb, yb, g_n, gbuf, 1, self.theta, 0, on_block_done=hook if not fd else None)
-                loss_all[done:done + g_n].copy_(self.loss[:g_n])
-                correct_all[done:done + g_n].copy_(self.correct[:g_n])
-                n_passes = 1
-                if overlap:
-                    ready = torch.cuda.current_stream().record_event()
-                    with torch.cuda.stream(self.wstream):
-                        self.wstream.wait_event(ready)
-                        self._fold(gbuf, g_n, 0, P, counter0 + done, sq_all[done:done + g_n], self.acc_ws)
-                elif not fd and batch_clip is not None:
-                    call("fb_mt_sqnorm", self.g.data_ptr(), P, g_n, P, 1.0, None, 0.0, self.sq.data_ptr(), self.mt_ws.data_ptr())
-                    call("fb_mt_chunk_clip", self.g.data_ptr(), P, g_n, P, self.sq.data_ptr(), float(batch_clip), self.clipped.data_ptr())
-                    call("fb_mt_accumulate", self.avg.data_ptr(), self.g.data_ptr(), P, g_n, P, counter0 + done, None, self.mt_ws.data_ptr())
-                elif not fd:
-                    # (with an early late bucket the slice [lb, P) has been folded on the side stream; |g_k|^2 is the sum of the two parts)
-                    self._fold(self.g, g_n, 0, lb if early else P, counter0 + done, self.sq, self.mt_ws)
-                    if early:
-                        torch.cuda.current_stream().wait_stream(self.side)
-                        self.sq[:g_n].add_(self.sq_late[:g_n])
-                else:
-                    s = 1.0 if legacy else float(block_strength)
-                    # finite-difference direction v = s*g_k + acc*pre (modules.py:217-221; the legacy variant ignores pre, :243-245)
-                    vpre, vacc = (None, 0.0) if (legacy or pre is None) else (pre.data_ptr(), float(acc_strength))
-                    call("fb_mt_sqnorm", self.g.data_ptr(), P, g_n, P, 1.0, None, 0.0, self.sq.data_ptr(), self.mt_ws.data_ptr())
-                    call("fb_mt_sqnorm", self.g.data_ptr(), P, g_n, P, s, vpre, vacc, self.vnorm2.data_ptr(), self.mt_ws.data_ptr())
-                    call("fb_mt_fd_perturb", self.theta.data_ptr(), self.g.data_ptr(), P, g_n, P, s, float(eps), 0.5 if central else 1.0,
+            hook = finish_late if early else None
+            self.group_gradient(xb, yb, g_n, gbuf, 1, self.theta, 0, on_block_done=hook if not fd else None)
+            loss_all[done:done + g_n].copy_(self.loss[:g_n])
+            correct_all[done:done + g_n].copy_(self.correct[:g_n])
+            n_passes = 1
+            if overlap:
+                ready = torch.cuda.current_stream().record_event()
+                with torch.cuda.stream(self.wstream):
+                    self.wstream.wait_event(ready)
+                    call("fb_mt_accumulate", self.avg.data_ptr(), gbuf.data_ptr(), P, g_n, P, counter0 + done, sq_all[done:done + g_n].data_ptr(),
+                         self.acc_ws.data_ptr())
+            elif not fd and batch_clip is not None:
+                call("fb_mt_sqnorm", self.g.data_ptr(), P, g_n, P, 1.0, None, 0.0, self.sq.data_ptr(), self.mt_ws.data_ptr())
+                call("fb_mt_chunk_clip", self.g.data_ptr(), P, g_n, P, self.sq.data_ptr(), float(batch_clip), self.clipped.data_ptr())
+                call("fb_mt_accumulate", self.avg.data_ptr(), self.g.data_ptr(), P, g_n, P, counter0 + done, None, self.mt_ws.data_ptr())
+            elif not fd:
+                # (with an early late bucket the slice [lb, P) has been folded on the side stream; |g_k|^2 is the sum of the two parts)
+                call("fb_mt_accumulate", self.avg.data_ptr(), self.g.data_ptr(), P, g_n, lb if early else P, counter0 + done, self.sq.data_ptr(),
+                     self.mt_ws.data_ptr())
+                if early:
+                    torch.cuda.current_stream().wait_stream(self.side)
+                    self.sq[:g_n].add_(self.sq_late[:g_n])
+            else:
+                s = 1.0 if legacy else float(block_strength)
+                # finite-difference direction v = s*g_k + acc*pre (modules.py:217-221; the legacy variant ignores pre, :243-245)
+                vpre, vacc = (None, 0.0) if (legacy or pre is None) else (pre.data_ptr(), float(acc_strength))
+                call("fb_mt_sqnorm", self.g.data_ptr(), P, g_n, P, 1.0, None, 0.0, self.sq.data_ptr(), self.mt_ws.data_ptr())
+                call("fb_mt_sqnorm", self.g.data_ptr(), P, g_n, P, s, vpre, vacc, self.vnorm2.data_ptr(), self.mt_ws.data_ptr())
+                call("fb_mt_fd_perturb", self.theta.data_ptr(), self.g.data_ptr(), P, g_n, P, s, float(eps), 0.5 if central else 1.0,
+                     self.vnorm2.data_ptr(), self.eps_n.data_ptr(), vpre, vacc, self.theta_k.data_ptr())
+                self.prep_weights(self.theta_k, g_n, per_chunk=True)
+                self.group_gradient(xb, yb, g_n, self.g_fd[0], 2, self.theta_k, 1, on_block_done=None if central else hook)
+                n_passes = 2
+                if central:
+                    call("fb_mt_fd_perturb", self.theta.data_ptr(), self.g.data_ptr(), P, g_n, P, s, float(eps), -0.5,
                          self.vnorm2.data_ptr(), self.eps_n.data_ptr(), vpre, vacc, self.theta_k.data_ptr())
                     self.prep_weights(self.theta_k, g_n, per_chunk=True)
-                    self.group_gradient(xb, yb, g_n, self.g_fd[0], 2, self.theta_k, 1, on_block_done=None if central else hook)
-                    n_passes = 2
-                    if central:
-                        call("fb_mt_fd_perturb", self.theta.data_ptr(), self.g.data_ptr(), P, g_n, P, s, float(eps), -0.5,
-                             self.vnorm2.data_ptr(), self.eps_n.data_ptr(), vpre, vacc, self.theta_k.data_ptr())
-                        self.prep_weights(self.theta_k, g_n, per_chunk=True)
-                        self.group_gradient(xb, yb, g_n, self.g_fd[1], 2, self.theta_k, 2, on_block_done=hook)
-                        n_passes = 3
-                    gb = self.g_fd[1] if central else self.g                 # vhp = (g(theta+) - g(theta-)) / eps_n  or  (g(theta+) - g) / eps_n
-                    if batch_clip is None:
-                        call("fb_mt_fd_combine_accumulate", self.avg.data_ptr(), self.g.data_ptr(), self.g_fd[0].data_ptr(), gb.data_ptr(), P, g_n,
-                             lb if early else P, self.eps_n.data_ptr(), cf, counter0 + done)
-                        if early:
-                            torch.cuda.current_stream().wait_stream(self.side)
-                    else:      # the regularised chunk gradients are materialised, clipped one by one, then averaged
-                        call("fb_mt_fd_combine", self.g.data_ptr(), self.g_fd[0].data_ptr(), gb.data_ptr(), P, g_n, P, self.eps_n.data_ptr(), cf)
-                        call("fb_mt_sqnorm", self.g.data_ptr(), P, g_n, P, 1.0, None, 0.0, self.vnorm2.data_ptr(), self.mt_ws.data_ptr())
-                        call("fb_mt_chunk_clip", self.g.data_ptr(), P, g_n, P, self.vnorm2.data_ptr(), float(batch_clip), self.clipped.data_ptr())
-                        call("fb_mt_accumulate", self.avg.data_ptr(), self.g.data_ptr(), P, g_n, P, counter0 + done, None, self.mt_ws.data_ptr())
-                if not overlap:
-                    sq_all[done:done + g_n].copy_(self.sq[:g_n])
-                if batch_clip is not None:
-                    self.clipped_all[done:done + g_n].copy_(self.clipped[:g_n])
-                call("fb_bn_running_update", self.running_mean.data_ptr(), self.running_var.data_ptr(), self.mean_tab.data_ptr(),
-                     self.var_tab.data_ptr(), n_passes, self.G * self.plan.ch_total, self.unbias.data_ptr(), g_n, self.plan.ch_total,
-                     BN_MOMENTUM)
-                self.num_batches_tracked += g_n * n_passes
-                done += g_n
-            if overlap:
-                torch.cuda.current_stream().wait_stream(self.wstream)
-        finally:                                     # (an exception inside a group must not leave later group_gradient / evaluate calls chained)
-            self.chain_on = False
+                    self.group_gradient(xb, yb, g_n, self.g_fd[1], 2, self.theta_k, 2, on_block_done=hook)
+                    n_passes = 3
+                gb = self.g_fd[1] if central else self.g                 # vhp = (g(theta+) - g(theta-)) / eps_n  or  (g(theta+) - g) / eps_n
+                if batch_clip is None:
+                    call("fb_mt_fd_combine_accumulate", self.avg.data_ptr(), self.g.data_ptr(), self.g_fd[0].data_ptr(), gb.data_ptr(), P, g_n,
+                         lb if early else P, self.eps_n.data_ptr(), cf, counter0 + done)
+                    if early:
+                        torch.cuda.current_stream().wait_stream(self.side)
+                else:      # the regularised chunk gradients are materialised, clipped one by one, then averaged
+                    call("fb_mt_fd_combine", self.g.data_ptr(), self.g_fd[0].data_ptr(), gb.data_ptr(), P, g_n, P, self.eps_n.data_ptr(), cf)
+                    call("fb_mt_sqnorm", self.g.data_ptr(), P, g_n, P, 1.0, None, 0.0, self.vnorm2.data_ptr(), self.mt_ws.data_ptr())
+                    call("fb_mt_chunk_clip", self.g.data_ptr(), P, g_n, P, self.vnorm2.data_ptr(), float(batch_clip), self.clipped.data_ptr())
+                    call("fb_mt_accumulate", self.avg.data_ptr(), self.g.data_ptr(), P, g_n, P, counter0 + done, None, self.mt_ws.data_ptr())
+            if not overlap:
+                sq_all[done:done + g_n].copy_(self.sq[:g_n])
+            if batch_clip is not None:
+                self.clipped_all[done:done + g_n].copy_(self.clipped[:g_n])
+            call("fb_bn_running_update", self.running_mean.data_ptr(), self.running_var.data_ptr(), self.mean_tab.data_ptr(),
+                 self.var_tab.data_ptr(), n_passes, self.G * self.plan.ch_total, self.unbias.data_ptr(), g_n, self.plan.ch_total,
+                 BN_MOMENTUM)
+            self.num_batches_tracked += g_n * n_passes
+            done += g_n
+        if overlap:
+            torch.cuda.current_stream().wait_stream(self.wstream)
         return loss_all, correct_all, sq_all
-
-    def check_device_errors(self):
-        """Raises if a kernel left its sticky error word (fb_bn_bwd_fused: a cluster waited ~2 s for workgroups that never became resident)."""
-        if int(self.bnf_sync[-1]) != 0:
-            self.bnf_sync[-1] = 0
-            raise lib.EngineError("fb_bn_bwd_fused: a workgroup cluster timed out waiting for its reduction (results of that launch are invalid); "
-                                  "FB_BN_BWD_FUSED=0 selects the two-pass BatchNorm backward")
 
     def grad_and_param_sqnorm(self):
         """Device tensor [|avg|^2, |theta|^2] (clip norm, reference training.py:202-204; param_norm, :92)."""

@@ -10,7 +10,7 @@ import struct
 import torch
 
 FB_F32, FB_BF16 = 0, 1
-EXPECTED_ABI = 16         # fb_abi_version() this package was written for (older libraries lack the entry-point table load() binds from)
+EXPECTED_ABI = 17         # fb_abi_version() this package was written for (older libraries lack the entry-point table load() binds from)
 _LIB_PATH = os.environ.get("FB_LIB_PATH") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "libfbengine.so")     # (FB_LIB_PATH: A/B builds, tools/build_variant.py)
 
 c_void_p, c_int, c_i64, c_float, c_double = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_double
@@ -35,7 +35,7 @@ class WgradArgs(C.Structure):
 # signature codes of the library's entry-point table (fb_entry_sig, include/fb_engine.h) -> ctypes
 _CTYPES = {"v": None, "i": c_int, "l": c_i64, "f": c_float, "d": c_double, "p": c_void_p, "s": C.c_char_p,
            "C": C.POINTER(ConvArgs), "W": C.POINTER(WgradArgs)}
-PROF_CLASSES = ("igemm_fwd", "igemm_dgrad", "wgrad", "bn_apply", "bn_bwd_reduce", "bn_bwd_apply", "bn_bwd_fused")
+PROF_CLASSES = ("igemm_fwd", "igemm_dgrad", "wgrad", "bn_apply", "bn_bwd_reduce", "bn_bwd_apply")
 PROF_KERNELS = {0: "?", 1: "conv_igemm_kernel (register-staged)", 2: "conv_igemm_v3_kernel", 3: "conv3x3s1_halo4_kernel", 4: "conv3x3s1_c64_halo5_kernel",
                 5: "conv3x3s2_dgrad_quad_kernel", 6: "conv1x1_k32_kernel", 7: "conv1x1_stream_kernel", 8: "conv3x3s2_fwd_kernel", 9: "conv1x1_pipe_kernel", 10: "conv1x1_gemm_kernel",
                 16: "conv_wgrad_kernel", 17: "conv_wgrad3x3_kernel", 18: "conv_wgrad3x3_v2_kernel", 19: "conv_wgrad1x1_kernel"}

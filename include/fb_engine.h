@@ -58,9 +58,9 @@ int32_t fb_abi_constant(const char* name);
 /* Optional measurement aid (the only process-global state in the library, off by default): while enabled every
  * fb_conv2d / fb_conv2d_wgrad launch is bracketed by HIP events recorded on the launch stream.  fb_profile_read waits
  * for the recorded launches and returns, per kernel class {0: igemm fwd, 1: igemm dgrad, 2: wgrad, 3: BN apply, 4: BN backward reduce,
- * 5: BN backward apply, 6: fused BN backward}, the summed elapsed milliseconds, the number of launches and the number of launches that
+ * 5: BN backward apply}, the summed elapsed milliseconds, the number of launches and the number of launches that
  * were not recorded (pool exhausted): three arrays of FB_PROF_CLASSES elements. */
-#define FB_PROF_CLASSES 7
+#define FB_PROF_CLASSES 6
 #define FB_PROF_INFO 11   /* shape words filed with a launch (fb_profile_read_launches) */
 int fb_profile_enable(int on, int capacity);
 int fb_profile_read(double* ms, int64_t* launches, int64_t* dropped);
@@ -157,15 +157,6 @@ typedef struct {
 } fb_wgrad_args;
 int32_t fb_wgrad_bn_fused_supported(const fb_wgrad_args* a);
 int fb_conv2d_wgrad(const fb_wgrad_args* a, void* stream);
-/* Chunk-chained weight gradient (ABI v12; bf16, 3x3 / stride 1 / pad 1 on 4x4 maps, chunks = imgs_per_group of 4k images;
- * fb_wgrad_chain_supported): the SUM over the chunks of what fb_conv2d_wgrad writes per chunk, plus every chunk's sum of squares -- the two
- * things the accumulate-over-all-chunks loop keeps of a chunk gradient (running mean: reference training.py:45-47,163-165; grad_norms:
- * training.py:162).  Workgroup (tile, s) walks chunks s, s + n_chains, ... and writes ONE fp32 tile:
- *   slabs   [n_chains][Cd][9][Cs]        partial sums; fb_wgrad_reduce(slabs, out, 0, 1, n_chains, Cd, 9, Cs, Cs) adds them in fixed order
- *   sq_part [n_img/imgs_per_group][(Cd/64)*(Cs/64)][8]   per chunk: partial sums of squares of that chunk's gradient (sum them per chunk)
- * a->dw_partial, split_k and group_stride are ignored.  The sum differs from adding the per-chunk results one by one only in rounding. */
-int32_t fb_wgrad_chain_supported(const fb_wgrad_args* a);
-int fb_conv2d_wgrad_chain(const fb_wgrad_args* a, int32_t n_chains, float* slabs, float* sq_part, void* stream);
 
 /* Workspace sizes (in floats) of the caller-owned scratch buffers the entry points below take; host-side arithmetic only,
  * no launch.  The library never allocates device memory.
@@ -246,21 +237,6 @@ int fb_bn_bwd_reduce2(const void* dout, const void* mask, const void* x_a, const
                       int64_t n_pixels, int32_t C, int64_t pixels_per_group, int32_t dtype, void* stream);
 int fb_bn_bwd_apply2(const void* dout, const void* mask, const void* x_a, const float* coef_a, void* dx_a, const void* x_b, const float* coef_b,
                      void* dx_b, int64_t n_pixels, int32_t C, int64_t pixels_per_group, int32_t dtype, void* stream);
-/* The three calls above in ONE pass over (dout, x) (csrc/bn_bwd_fused.hip; autograd's native_batch_norm_backward + threshold_backward behind
- * resnets.py:214-230): a cluster of workgroups that is resident as a whole keeps a statistics group's operands in registers between the
- * reduction and the apply step -- 3 tensor passes instead of 5.  Same arithmetic as reduce / finalize / apply (fp32 sums per thread, partial
- * rows added in fixed order in double, dx = c_dy*dy + c_x*x + c_0); the result does not depend on how many groups a launch holds.
- * fb_bn_bwd_fused_supported(): 0 where the shape is not for it (a group's vectors must tile 4096-vector slices and its cluster must fit the
- * device's 2 x #CU resident workgroups) -- the caller then takes the three-call form.  `partial`: fb_ws_bn_bwd_fused_floats() floats;
- * `sync`: fb_ws_bn_bwd_fused_ints(n_groups) int32, ZEROED once by the caller (the last word is a sticky error flag: a wait of ~2 s -- a
- * cluster that never became resident -- sets it instead of hanging the device). */
-int32_t fb_bn_bwd_fused_supported(int64_t n_pixels, int32_t C, int64_t pixels_per_group, int32_t dtype);
-int64_t fb_ws_bn_bwd_fused_floats(int64_t n_pixels, int32_t C, int64_t pixels_per_group, int32_t dtype);
-int64_t fb_ws_bn_bwd_fused_ints(int64_t n_groups);
-int fb_bn_bwd_fused(const void* dout, const void* mask, const void* x, const float* mean_tab, const float* invstd, const float* scale,
-                    int32_t ch_total, int32_t ch_off, float* dgamma, float* dbeta, int64_t grad_group_stride, float* coef, void* dx,
-                    void* dy_out, int64_t n_pixels, int32_t C, int64_t pixels_per_group, double count, int32_t dtype, float* partial,
-                    int32_t* sync, void* stream);
 
 /* ---------------------------------------------------------------- data path --------------------------------------- */
 /* Stem patch gather: images [n_img][C][H][W] fp32 (device) -> patches [n_img][Ho][Wo][cin_pad] in `dtype`, element tap*C + c
@@ -325,14 +301,6 @@ int fb_mt_sqnorm(const float* x, int64_t group_stride, int32_t n_groups, int64_t
  * If sq_out != NULL also writes sq_out[j] = |g[j]|^2 (fused, one pass). */
 int fb_mt_accumulate(float* avg, const float* g, int64_t group_stride, int32_t n_groups, int64_t n, int32_t counter0,
                      float* sq_out, float* ws, void* stream);
-/* the running mean advanced by n_groups chunks at once from their SUM (fb_conv2d_wgrad_chain + fb_wgrad_reduce):
- * avg += (gsum - n_groups*avg) / (counter0 + n_groups) -- what n_groups steps of fb_mt_accumulate's recurrence amount to (ABI v12) */
-int fb_mt_accumulate_sum(float* avg, const float* gsum, int64_t n, int32_t counter0, int32_t n_groups, void* stream);
-/* fb_mt_accumulate over [0, n) except up to four ranges [lo_k, hi_k) (multiples of 4 floats; lo == hi: unused), which are neither read nor
- * written and do not enter sq_out: the layers whose mean comes from fb_mt_accumulate_sum (ABI v12) */
-int fb_mt_accumulate_skip(float* avg, const float* g, int64_t group_stride, int32_t n_groups, int64_t n, int32_t counter0, float* sq_out,
-                          float* ws, int64_t lo0, int64_t hi0, int64_t lo1, int64_t hi1, int64_t lo2, int64_t hi2, int64_t lo3, int64_t hi3,
-                          void* stream);
 /* eps_n[g] = eps / sqrt(vnorm2[g]);  theta_out[g] = theta0 + (sign*eps_n[g]) * (s*g[g] + acc*pre)   (modules.py:217-226;
  * pre = the pre-computed full gradient of the acc_strength pre-pass, training.py:128-142, NULL without it) */
 int fb_mt_fd_perturb(const float* theta0, const float* g, int64_t group_stride, int32_t n_groups, int64_t n, float s,

@@ -326,15 +326,6 @@ def fd_perturb_ref(theta0, g, s, alpha, pre=None, acc=0.0):
     return out, U32 * (theta0.double().abs() + 3 * abs(alpha) * mag + out.abs())
 
 
-def accumulate_sum_ref(a, gsum, counter0, n_groups):
-    """fb_mt_accumulate_sum: a + (gsum - G a) / (c + G): (out, u (4 (|gsum| + G |a|) / (c + G) + |out|)) -- G a, the difference, the product with
-    the fp32-rounded 1/(c+G) and that rounding; the sum."""
-    a, gsum = a.double(), gsum.double()
-    inv = 1.0 / (counter0 + n_groups)
-    out = a + (gsum - n_groups * a) * inv
-    return out, U32 * (4 * (gsum.abs() + n_groups * a.abs()) * inv + out.abs())
-
-
 def scale_ref(x, a):
     """fb_mt_scale / the clip-free product: ONE correctly rounded fp32 product: (a x, u |a x|)."""
     out = f32r(a) * x.double()

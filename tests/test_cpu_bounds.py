@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests.helpers import (U32, accumulate_sum_ref, clip_coef_ref, distinct_rows, f32r, fd_combine_ref, fd_perturb_ref, norm_bias_ref, reduction_bound,
+from tests.helpers import (U32, clip_coef_ref, distinct_rows, f32r, fd_combine_ref, fd_perturb_ref, norm_bias_ref, reduction_bound,
                            running_mean_ref, sam_ref, sgd_ref, within_bound)
 
 N, G = 1_000_002, 98
@@ -238,7 +238,7 @@ def test_scalar_rule_references_use_fp32_rounded_scalars(sgd_inputs):
     assert r_bad > r_good and 0.05 < shift <= 0.25
 
 
-def test_remaining_elementwise_references_accept_honest_fp32(sgd_inputs, rows):
+def test_remaining_elementwise_references_accept_honest_fp32(sgd_inputs):
     p, g, m, _ = sgd_inputs
     # fb_mt_fd_perturb
     s, acc, eps = 0.5, 0.3, 1e-2
@@ -252,13 +252,6 @@ def test_remaining_elementwise_references_accept_honest_fp32(sgd_inputs, rows):
     bad = out.clone()
     bad[N - N % 4:] = p[N - N % 4:]
     assert within_bound(bad, *fd_perturb_ref(p, g, s, -0.5 * eps_n64, m, acc))[0] > 1.0
-    # fb_mt_accumulate_sum
-    gsum = rows.double().sum(0).float()
-    a = m
-    got = a + (gsum - _f(float(G)) * a) * _f(1.0 / (292 + G))
-    r, b = accumulate_sum_ref(a, gsum, 292, G)
-    assert within_bound(got, r, b)[0] <= 1.0
-    assert within_bound(a + (gsum - _f(float(G)) * a) * _f(1.0 / (291 + G)), r, b)[0] > 1.0
     # fb_mt_sam_ascent (clip hit and not)
     norm2 = float(np.float32(float(g.double().pow(2).sum())))
     for clip in (None, 0.5 * norm2 ** 0.5):

@@ -141,10 +141,10 @@ def test_check_scope_refuses_more_than_one_rank(monkeypatch):
 # ---------------------------------------------------------------------------------------------------------------- entry table --
 def test_entry_table_lists_the_sgd_entry_points():
     """``fb_mt_sgd_prep`` / ``fb_mt_sgd_torch`` with the signatures the compiler derived from the header's prototypes, recordable; the
-    ``_supported`` query is a host function; the library and the binding are at ABI 16."""
+    ``_supported`` query is a host function; the library and the binding are at ABI 17."""
     from fullbatchtraining_amd import lib
     h = lib.load()
-    assert lib.EXPECTED_ABI == 16 == h.fb_abi_version()
+    assert lib.EXPECTED_ABI == 17 == h.fb_abi_version()
     table = {h.fb_entry_name(i).decode(): (h.fb_entry_sig(i).decode(), h.fb_entry_kind(i)) for i in range(h.fb_entry_count())}
     #          theta grad mom n gnorm2 clip lr wd mu damp nesterov first | tab n_layers w_fwd w_dgrad dtype | stream
     assert table["fb_mt_sgd_prep"] == ("i:ppplpfffffii" + "pippi" + "p", 2)

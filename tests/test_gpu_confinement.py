@@ -510,31 +510,6 @@ def test_conv_wgrad_stem_fp16x2(cin_pad, hw, ipg, groups, split_k):
     _wgrad_case(F32, cin_pad, 64, 1, 1, hw, ipg, groups, split_k, amax=True, want=16)
 
 
-@pytest.mark.parametrize("cin,cout,ipg,chunks,chains", [(64, 64, 8, 5, 2), (128, 64, 16, 7, 3), (64, 128, 4, 6, 6), (256, 128, 12, 3, 1)])
-def test_conv_wgrad_chain(cin, cout, ipg, chunks, chains):
-    """fb_conv2d_wgrad_chain: ``slabs`` [n_chains][Cd][9][Cs] and ``sq_part`` [chunks][tiles][8] carved; against float64 per-chunk gradients (tolerances of
-    test_conv_wgrad_chunk_chain)"""
-    lib = _lib()
-    gen = _gen(cin + cout + ipg)
-    n = ipg * chunks
-    x, dy = _randn(gen, n, 4, 4, cin, dtype=BF16), _randn(gen, n, 4, 4, cout, dtype=BF16)
-    tiles = (cout // 64) * (cin // 64)
-
-    def args(o):
-        return lib.WgradArgs(_p(o.get("x")), _p(o.get("dy")), None, n, 4, 4, cin, 4, 4, cout, 3, 3, 1, 1, ipg, 1, lib.dtype_code(BF16), 0)
-    assert lib.load().fb_wgrad_chain_supported(C.byref(args({"x": x, "dy": dy})))
-
-    def fn(o):
-        _call("fb_conv2d_wgrad_chain", C.byref(args(o)), chains, o["slabs"], o["sq_part"])
-    got = confined(fn, {"x": x, "dy": dy}, {"slabs": ((chains, cout, 9, cin), F32), "sq_part": ((chunks, tiles, 8), F32)})
-    per = torch.stack([torch.nn.grad.conv2d_weight(_nchw64(x[g * ipg:(g + 1) * ipg]), (cout, cin, 3, 3), _nchw64(dy[g * ipg:(g + 1) * ipg]), 1, 1).permute(0, 2, 3, 1)
-                       for g in range(chunks)]).reshape(chunks, cout, 9, cin)
-    for s_ in range(chains):
-        assert rel(got["slabs"][s_], per[s_::chains].sum(0)) < 2e-6
-    sq, ref = got["sq_part"].double().sum((1, 2)), per.pow(2).sum((1, 2, 3))
-    assert float(((sq - ref).abs() / ref).max()) < 1e-5
-
-
 @pytest.mark.parametrize("groups,split_k,cd,taps,cs_pad,cs_real,gap", [(2, 3, 64, 9, 32, 27, 40), (3, 1, 64, 1, 160, 147, 8), (1, 5, 128, 9, 64, 64, 0), (2, 2, 64, 9, 64, 64, 100)])
 def test_wgrad_reduce(groups, split_k, cd, taps, cs_pad, cs_real, gap):
     """the fixed-order sum of the split_k slabs with the channel padding dropped, into rows out_group_stride apart: the gap stays untouched"""
@@ -768,53 +743,6 @@ def test_bn_bwd_reduce2_apply2(dtype, C_, W):
         assert rel(got["dx_a" if k_ == 0 else "dx_b"].view(groups, -1, C_), ref) < tol(dtype, 0.5)
 
 
-# (C, map width, images per group, groups): those of test_bn_bwd_fused_equals_the_two_pass_form, and widths 4 and 7 with groups whose vectors tile 4096-vector slices
-# (7 x 7 maps of 64 channels: 512 images per group)
-FUSED_SHAPES = [(64, 16, 32, 5), (128, 8, 64, 3), (512, 2, 128, 4), (64, 32, 128, 3), (512, 4, 128, 3), (64, 7, 512, 2)]
-
-
-@pytest.mark.parametrize("dtype", [F32, BF16])
-def test_bn_bwd_fused(dtype):
-    """(a group's vectors must tile 4096-vector slices and its cluster must fit the device: which of the shapes that is depends on the CU count; one at least)"""
-    lib = _lib()
-    took = [shape for shape in FUSED_SHAPES if lib.load().fb_bn_bwd_fused_supported(shape[3] * shape[2] * shape[1] ** 2, shape[0], shape[2] * shape[1] ** 2, lib.dtype_code(dtype))]
-    assert {shape[1] for shape in took} >= {32, 16, 8, 4, 7}, f"fb_bn_bwd_fused_supported takes only {took}"
-    for shape in took:
-        _bn_bwd_fused_case(dtype, *shape)
-
-
-def _bn_bwd_fused_case(dtype, C_, hw, imgs, G):
-    """the one-pass cluster kernel where fb_bn_bwd_fused_supported: ``partial`` at fb_ws_bn_bwd_fused_floats (scratch), ``sync`` at fb_ws_bn_bwd_fused_ints --
-    inout: "`sync`: fb_ws_bn_bwd_fused_ints(n_groups) int32, ZEROED once by the caller" (include/fb_engine.h)"""
-    lib = _lib()
-    h = lib.load()
-    dtc = lib.dtype_code(dtype)
-    n = G * imgs
-    px, ppg = n * hw * hw, imgs * hw * hw
-    gen = _gen(C_ + hw)
-    x, dout = _randn(gen, n, hw, hw, C_, dtype=dtype), _randn(gen, n, hw, hw, C_, dtype=dtype)
-    bits, keep = _bits(gen, x.numel(), dtype)
-    xg = x.double().view(G, -1, C_)
-    mean, inv = xg.mean(1), (xg.var(1, unbiased=False) + 1e-5).rsqrt()
-    scale = (torch.rand(G, C_, device="cuda", generator=gen) + 0.5)
-    n_int = int(h.fb_ws_bn_bwd_fused_ints(G))
-
-    def fn(o):
-        _call("fb_bn_bwd_fused", o["dout"], o["mask"], o["x"], o["mean"], o["invstd"], o["scale"], C_, 0, o["grad"], o["grad"].data_ptr() + 4 * C_, 2 * C_ + 32, o["coef"],
-              o["dx"], o["dy_out"], px, C_, ppg, float(ppg), dtc, o["partial"], o["sync"])
-    got = confined(fn, {"dout": dout, "mask": bits, "x": x, "mean": mean.float().contiguous(), "invstd": inv.float().contiguous(), "scale": scale},
-                   {"grad": Strided(G, 2 * C_, 2 * C_ + 32), "coef": ((G, C_, 3), F32), "dx": (x.shape, dtype), "dy_out": (x.shape, dtype)},
-                   inout={"sync": torch.zeros(n_int, dtype=torch.int32)}, scratch={"partial": ((int(h.fb_ws_bn_bwd_fused_floats(px, C_, ppg, dtc)),), F32)})
-    assert int(got["sync"][-1]) == 0, "a cluster timed out"
-    dyg = (dout.double() * keep.view(x.shape)).view(G, -1, C_)
-    xhat = (xg - mean[:, None]) * inv[:, None]
-    dbeta, dgamma = dyg.sum(1), (dyg * xhat).sum(1)
-    assert rel(got["grad"][:, :C_], dgamma) < 1e-4 and rel(got["grad"][:, C_:], dbeta) < 1e-4
-    dx = scale.double()[:, None] * (dyg - dbeta[:, None] / ppg - xhat * dgamma[:, None] / ppg)
-    assert rel(got["dx"].view(G, -1, C_), dx) < (1e-4 if dtype == F32 else 8e-3)
-    assert rel(got["dy_out"].view(G, -1, C_), dyg) < tol(dtype, 0.5)
-
-
 def test_bn_running_update_and_eval_coeffs():
     """C = 100 is no multiple of a wave; the running statistics are read-modify-write by definition (inout)"""
     from tests.helpers import bn_eval_coeffs_ref, bn_running_ref, within_bound
@@ -1035,8 +963,7 @@ EXCLUDED = {
     "fb_absmax": "guarded at arena size in tests/test_gpu_update_production.py",
     **{name: "fb_mt_*: guard columns checked at arena size in tests/test_gpu_update_production.py (padding_untouched)" for name in (
         "fb_mt_sqnorm", "fb_mt_accumulate", "fb_mt_fd_perturb", "fb_mt_fd_combine_accumulate", "fb_mt_fd_combine", "fb_mt_chunk_clip", "fb_mt_norms2", "fb_mt_clip_sgd",
-        "fb_mt_scale", "fb_mt_sam_ascent", "fb_mt_sam_restore", "fb_mt_absmax2", "fb_mt_pnorm2", "fb_mt_norm_bias", "fb_mt_ema", "fb_mt_clip_scale", "fb_mt_grad_noise",
-        "fb_mt_accumulate_sum", "fb_mt_accumulate_skip")},
+        "fb_mt_scale", "fb_mt_sam_ascent", "fb_mt_sam_restore", "fb_mt_absmax2", "fb_mt_pnorm2", "fb_mt_norm_bias", "fb_mt_ema", "fb_mt_clip_scale", "fb_mt_grad_noise")},
 }
 
 

@@ -414,67 +414,6 @@ def test_conv_wgrad(dtype, cin, cout, k, stride, hw, ipg, groups, split, monkeyp
         assert bool(torch.isnan(arena[:, :8]).all()) and bool(torch.isnan(arena[:, 8 + cout * k * k * cin:]).all())
 
 
-def test_mt_accumulate_skip_and_sum():
-    """fb_mt_accumulate_skip = fb_mt_accumulate with up to four ranges left alone (mean untouched there, norms without them);
-    fb_mt_accumulate_sum = the same recurrence advanced by a group's chunks at once from their sum."""
-    lib = _lib()
-    torch.manual_seed(3)
-    P, G, c0 = 4096 + 64, 5, 3
-    g = torch.randn(G, P, device="cuda")
-    avg0 = torch.randn(P, device="cuda")
-    ws = torch.zeros(int(lib.load().fb_ws_mt_floats(G)), device="cuda")
-    ref, sq_ref = avg0.clone(), torch.zeros(G, device="cuda")
-    lib.call("fb_mt_accumulate", ref.data_ptr(), g.data_ptr(), P, G, P, c0, sq_ref.data_ptr(), ws.data_ptr())
-    skips = [(128, 640), (1024, 1028), (4000, 4160)]
-    got, sq = avg0.clone(), torch.zeros(G, device="cuda")
-    flat = [v for r in skips for v in r] + [0, 0]
-    lib.call("fb_mt_accumulate_skip", got.data_ptr(), g.data_ptr(), P, G, P, c0, sq.data_ptr(), ws.data_ptr(), *flat)
-    keep = torch.ones(P, dtype=torch.bool, device="cuda")
-    for a, b in skips:
-        keep[a:b] = False
-    assert torch.equal(got[keep], ref[keep]) and torch.equal(got[~keep], avg0[~keep])
-    want = (g.double() ** 2 * keep).sum(1)
-    assert float(((sq.double() - want).abs() / want).max()) < 1e-6
-    # the skipped ranges from the group sum: what G steps of the recurrence amount to
-    for a, b in skips:
-        gs = g[:, a:b].sum(0).contiguous()
-        part = avg0[a:b].clone()
-        lib.call("fb_mt_accumulate_sum", part.data_ptr(), gs.data_ptr(), b - a, c0, G)
-        assert float((part.double() - ref[a:b].double()).abs().max()) < 2e-6 * float(ref[a:b].abs().max() + 1)
-
-
-@pytest.mark.parametrize("cin,cout,ipg,chunks,chains", [(64, 64, 8, 5, 2), (128, 64, 16, 7, 3), (64, 128, 4, 6, 6), (512, 512, 128, 9, 4), (256, 128, 12, 3, 1)])
-def test_conv_wgrad_chunk_chain(cin, cout, ipg, chunks, chains):
-    """fb_conv2d_wgrad_chain (ABI v12): the sum over the chunks of the per-chunk weight gradients and every chunk's sum of squares, against the
-    per-chunk kernel (whose chunk gradients are held to torch by test_conv_wgrad): same products, the sum taken in another order."""
-    lib = _lib()
-    torch.manual_seed(5)
-    n = ipg * chunks
-    x = q(torch.randn(n, cin, 4, 4), torch.bfloat16)
-    dy = q(torch.randn(n, cout, 4, 4), torch.bfloat16)
-    xd, dyd = nhwc(x).to(torch.bfloat16).cuda(), nhwc(dy).to(torch.bfloat16).cuda()
-    per = torch.full((chunks, 1, cout, 9, cin), float("nan"), device="cuda")
-    lib.conv2d_wgrad(xd, dyd, per, 3, 3, 1, 1, ipg, 1)
-    per = per[:, 0].double()
-    a = lib.WgradArgs(xd.data_ptr(), dyd.data_ptr(), None, n, 4, 4, cin, 4, 4, cout, 3, 3, 1, 1, ipg, 1, lib.dtype_code(torch.bfloat16), 0)
-    assert lib.load().fb_wgrad_chain_supported(lib.C.byref(a))
-    tiles = (cout // 64) * (cin // 64)
-    slabs = torch.full((chains, cout, 9, cin), float("nan"), device="cuda")
-    sqp = torch.full((chunks, tiles, 8), float("nan"), device="cuda")
-    lib.call("fb_conv2d_wgrad_chain", lib.C.byref(a), chains, slabs.data_ptr(), sqp.data_ptr())
-    total = torch.full((cout, 9, cin), float("nan"), device="cuda")
-    lib.wgrad_reduce(slabs, total, 0, 1, chains, cout, 9, cin, cin)
-    want = per.sum(0)
-    assert float((total.double() - want).norm() / want.norm()) < 2e-6
-    sq = sqp.double().sum((1, 2))
-    ref = per.pow(2).sum((1, 2, 3))
-    assert float(((sq - ref).abs() / ref).max()) < 1e-5, (sq, ref)
-    # a chain's slab = the sum of ITS chunks
-    for s_ in range(chains):
-        w = per[s_::chains].sum(0)
-        assert float((slabs[s_].double() - w).norm() / w.norm()) < 2e-6
-
-
 @pytest.mark.parametrize("magnitude", [1.0, 2e-6])
 @pytest.mark.parametrize("cin,cout,k,stride,hw,ipg,groups,split", [(64, 64, 3, 1, 8, 8, 2, 3), (64, 128, 3, 2, 8, 8, 1, 2), (256, 256, 3, 1, 4, 16, 2, 1),
                                                                   (128, 256, 1, 1, 4, 16, 1, 2), (32, 64, 1, 1, 8, 4, 2, 1), (64, 64, 3, 1, 32, 4, 2, 2),
@@ -1309,70 +1248,6 @@ def test_head_tta_vs_reference_formula(n, classes):
     got_loss, got_correct = ws[2 * n:].tolist()
     assert abs(got_loss - float(loss_sum)) < 1e-5 * max(1.0, float(loss_sum)), (got_loss, float(loss_sum))
     assert got_correct == float(correct)
-
-
-@pytest.mark.parametrize("dtype", DTYPES)
-@pytest.mark.parametrize("C,hw,imgs,G", [(64, 16, 32, 5), (128, 8, 64, 3), (512, 2, 128, 4), (64, 32, 128, 3)])
-def test_bn_bwd_fused_equals_the_two_pass_form(dtype, C, hw, imgs, G):
-    """fb_bn_bwd_fused (one pass over (dout, x): a resident cluster of workgroups keeps a statistics group's operands in registers between the
-    reduction and the apply step; off by default -- it measured slower, profiles/r4_notes.md) against fb_bn_bwd_reduce -> finalize -> apply on
-    the same inputs: same masked gradient bit for bit, dx / dgamma / dbeta to fp32 rounding (the pixel partition of the sums differs), and
-    against torch's native_batch_norm_backward through autograd."""
-    lib = _lib()
-    handle = lib.load()
-    dtc = lib.dtype_code(dtype)
-    n = G * imgs
-    px, ppg = n * hw * hw, imgs * hw * hw
-    if not handle.fb_bn_bwd_fused_supported(px, C, ppg, dtc):
-        pytest.skip("shape not for the cluster kernel")
-    torch.manual_seed(C + hw)
-    eb = 4 if dtype == torch.float32 else 2
-    x = torch.randn(n, hw, hw, C, device="cuda").to(dtype)
-    dout = torch.randn(n, hw, hw, C, device="cuda").to(dtype)
-    gamma = torch.rand(C, device="cuda") + 0.5
-    xg = x.float().view(G, imgs * hw * hw, C)
-    mean, var = xg.mean(1), xg.var(1, unbiased=False)
-    invstd = (var + 1e-5).rsqrt()
-    scale = gamma[None] * invstd
-    y = (xg - mean[:, None]) * scale[:, None] + 0.1                                  # the forward output whose ReLU mask the backward uses
-    keep = (y > 0)
-    bits = (keep.reshape(-1, 8).to(torch.int32) * (2 ** torch.arange(8, device="cuda", dtype=torch.int32))).sum(1).to(torch.uint8) if eb == 2 else \
-        (keep.reshape(-1, 4).to(torch.int32) * (2 ** torch.arange(4, device="cuda", dtype=torch.int32))).sum(1).to(torch.uint8)
-    out = {}
-    for mode in ("two-pass", "fused"):
-        dx, dy = torch.empty_like(x), torch.empty_like(x)
-        gout = torch.zeros(G, 2 * C, device="cuda")
-        coef = torch.zeros(G, C, 3, device="cuda")
-        if mode == "two-pass":
-            rows = handle.fb_bn_bwd_reduce_rows(px, ppg)
-            ws = torch.zeros(int(handle.fb_ws_bn_partial_floats(px, C)), device="cuda")
-            lib.call("fb_bn_bwd_reduce", dout.data_ptr(), None, bits.data_ptr(), x.data_ptr(), mean.data_ptr(), invstd.data_ptr(), C, 0, ws.data_ptr(), px, C, ppg, dtc)
-            lib.call("fb_bn_bwd_finalize", ws.data_ptr(), rows, G, C, float(ppg), scale.data_ptr(), mean.data_ptr(), invstd.data_ptr(), C, 0,
-                     gout.data_ptr(), gout.data_ptr() + 4 * C, 2 * C, coef.data_ptr(), 0)
-            lib.call("fb_bn_bwd_apply", dout.data_ptr(), None, bits.data_ptr(), x.data_ptr(), coef.data_ptr(), dx.data_ptr(), dy.data_ptr(), px, C, ppg, dtc, None, None)
-        else:
-            ws = torch.zeros(int(handle.fb_ws_bn_bwd_fused_floats(px, C, ppg, dtc)), device="cuda")
-            sync = torch.zeros(int(handle.fb_ws_bn_bwd_fused_ints(G)), device="cuda", dtype=torch.int32)
-            for _ in range(2):                                                       # (a second launch on the same workspace: counters and flags are re-armed)
-                lib.call("fb_bn_bwd_fused", dout.data_ptr(), bits.data_ptr(), x.data_ptr(), mean.data_ptr(), invstd.data_ptr(), scale.data_ptr(), C, 0,
-                         gout.data_ptr(), gout.data_ptr() + 4 * C, 2 * C, coef.data_ptr(), dx.data_ptr(), dy.data_ptr(), px, C, ppg, float(ppg), dtc,
-                         ws.data_ptr(), sync.data_ptr())
-            torch.cuda.synchronize()
-            assert int(sync[-1]) == 0, "a cluster timed out"
-        torch.cuda.synchronize()
-        out[mode] = (dx.float(), dy.float(), gout.clone())
-    a, b = out["fused"], out["two-pass"]
-    assert torch.equal(a[1], b[1])
-    tol = 1e-5 if dtype == torch.float32 else 6e-3                                   # bf16: one output rounding where a coefficient differs in its last bit
-    assert rel(a[0], b[0]) < tol and rel(a[2], b[2]) < 1e-5, (rel(a[0], b[0]), rel(a[2], b[2]))
-    # torch: d/dx and d/dgamma, d/dbeta of  relu-masked BatchNorm  with the same upstream gradient
-    xt = x.float().view(G, -1, C).clone().requires_grad_(True)
-    gm, bt = gamma.clone().requires_grad_(True), torch.full((C,), 0.1, device="cuda", requires_grad=True)
-    for g in range(G):
-        yt = torch.nn.functional.batch_norm(xt[g].t().reshape(1, C, -1), None, None, gm, bt, True, 0.0, 1e-5)
-        (yt * (dout.float().view(G, -1, C)[g] * keep[g]).t().reshape(1, C, -1)).sum().backward()
-    want = xt.grad.view_as(a[0])
-    assert rel(a[0], want) < (1e-4 if dtype == torch.float32 else 8e-3), rel(a[0], want)
 
 
 @pytest.mark.parametrize("dt", DTYPES)

@@ -17,7 +17,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests.helpers import (COEF_ROUNDINGS, SENTINEL, U32, accumulate_sum_ref, clip_coef_ref, distinct_rows, f32r, fd_combine_ref, fd_perturb_ref,
+from tests.helpers import (COEF_ROUNDINGS, SENTINEL, U32, clip_coef_ref, distinct_rows, f32r, fd_combine_ref, fd_perturb_ref,
                            make_data, norm_bias_ref, padding_untouched, reduction_bound, running_mean_ref, sam_ref, scale_ref, sgd_ref, within_bound)
 
 pytestmark = pytest.mark.gpu
@@ -118,7 +118,7 @@ def tol1(n):        # scalar reductions (a product and a sum per element), FB_MT
 
 
 # ------------------------------------------------------------------------------------------------------------------ group kernels --
-@exercises("fb_mt_accumulate", "fb_mt_accumulate_skip")
+@exercises("fb_mt_accumulate")
 @pytest.mark.parametrize("G,c0", [(98, 0), (98, 292), (13, 292)])
 def test_running_mean_and_chunk_norms(G, c0):
     n = N18
@@ -139,20 +139,6 @@ def test_running_mean_and_chunk_norms(G, c0):
     avg2 = a0.clone()
     mt("fb_mt_accumulate", avg2.data_ptr(), g.data_ptr(), STRIDE, G, n, c0, None, ws.data_ptr(), n=n)
     assert torch.equal(avg2, avg)                                    # the pass without the norms: the same bits
-    # four ranges left alone, at offsets that are multiples of 4 floats but not of 16 or 64; the rows are NaN there: never read
-    skips = [(0, 1728), (1_234_564, 1_234_564 + 589_824), (6_000_004, 8_359_300), (n - 2 - 5120, n - 2)]
-    mask = torch.zeros(n, dtype=torch.bool, device="cuda")
-    sq_skip = sq64.clone()
-    for lo, hi in skips:
-        assert lo % 4 == 0 and hi % 4 == 0 and 0 <= lo < hi <= n
-        mask[lo:hi] = True
-        sq_skip -= torch.stack([g[j, lo:hi].double().pow(2).sum() for j in range(G)])
-        g[:, lo:hi] = float("nan")
-    avg3, sq3 = a0.clone(), torch.zeros(G, device="cuda")
-    mt("fb_mt_accumulate_skip", avg3.data_ptr(), g.data_ptr(), STRIDE, G, n, c0, sq3.data_ptr(), ws.data_ptr(), *[v for r in skips for v in r], n=n)
-    report(f"fb_mt_accumulate_skip G={G} c0={c0} mean", *within_bound(avg3[:n], torch.where(mask, a0[:n].double(), ref), torch.where(mask, torch.zeros_like(B), B)))
-    report_rel(f"fb_mt_accumulate_skip G={G} c0={c0} chunk norms", sq3, sq_skip, tol4(n))
-    assert padding_untouched(avg3, n)
 
 
 @exercises("fb_mt_sqnorm", "fb_absmax")
@@ -276,7 +262,7 @@ def test_fd_recombination_and_chunk_clip(G, c0, central):
 
 
 # ---------------------------------------------------------------------------------------------------------- single-vector kernels --
-@exercises("fb_mt_norms2", "fb_mt_absmax2", "fb_mt_pnorm2", "fb_mt_sqnorm", "fb_absmax", "fb_mt_accumulate", "fb_mt_accumulate_sum")
+@exercises("fb_mt_norms2", "fb_mt_absmax2", "fb_mt_pnorm2", "fb_mt_sqnorm", "fb_absmax", "fb_mt_accumulate")
 @pytest.mark.parametrize("n", N_SINGLE)
 def test_vector_reductions_and_means(n):
     a, b, ws = vec(n, 1e-2, 31), vec(n, 1.0, 32), ws_for(2)
@@ -316,22 +302,15 @@ def test_vector_reductions_and_means(n):
         mt("fb_absmax", x.data_ptr() + 4, n - 1, 1, 0, 1, one.data_ptr(), n=n)
         assert float(one) == float(x[1:n].abs().max()), pos
     print(f"[update-production] fb_mt_absmax2 / fb_absmax n={n}: exact at 4 planted positions")
-    # the running mean of two rows and the mean advanced from a group sum, at this length
+    # the running mean of two rows at this length
     stride = (n + 63) // 64 * 64
     g = distinct_rows(2, n, stride, 1e-2, 33, "cuda")
     ws8 = ws_for(8)
-    ref, B, total = running_mean_ref(a[:n], (g[j, :n] for j in range(2)), 292)
+    ref, B, _ = running_mean_ref(a[:n], (g[j, :n] for j in range(2)), 292)
     avg, sq = a.clone(), torch.zeros(2, device="cuda")
     mt("fb_mt_accumulate", avg.data_ptr(), g.data_ptr(), stride, 2, n, 292, sq.data_ptr(), ws8.data_ptr(), n=n)
     report(f"fb_mt_accumulate n={n} G=2 mean", *within_bound(avg[:n], ref, B))
     report_rel(f"fb_mt_accumulate n={n} G=2 chunk norms", sq, torch.stack([g[j, :n].double().pow(2).sum() for j in range(2)]), tol4(n))
-    assert padding_untouched(avg, n)
-    gsum = torch.empty(n + PAD, device="cuda")
-    gsum[:n] = f32_of(total * 49.0)
-    gsum[n:] = SENTINEL
-    avg = a.clone()
-    mt("fb_mt_accumulate_sum", avg.data_ptr(), gsum.data_ptr(), n, 292, 98, n=n)
-    report(f"fb_mt_accumulate_sum n={n} G=98 c0=292", *within_bound(avg[:n], *accumulate_sum_ref(a[:n], gsum[:n], 292, 98)))
     assert padding_untouched(avg, n)
 
 
@@ -430,17 +409,14 @@ def _bucket_bound(eng, world):
     return (eng.plan.late_offset + granule - 1) // granule * granule
 
 
-@pytest.mark.parametrize("mode", ["fp32", "bf16", "bf16-chained"])
-def test_engine_fold_over_bucket_ranges(mode, monkeypatch):
-    """Engine._fold over [0, b) and [b, P) for the bucket boundary of world sizes 2, 3 and 8, counters 0 and 292, with and without the norms;
-    'bf16-chained': chain_on with gsum / chain_sq filled consistently (fb_mt_accumulate_sum + fb_mt_accumulate_skip at the real layer offsets), the
-    chained layers' rows of the arena NaN."""
+@pytest.mark.parametrize("mode", ["fp32", "bf16"])
+def test_engine_fold_over_bucket_ranges(mode):
+    """The running-mean fold of Engine.full_gradient (fb_mt_accumulate at arena offsets) over [0, b) and [b, P) for the bucket boundary of world sizes 2, 3
+    and 8, counters 0 and 292, with and without the norms."""
+    from fullbatchtraining_amd import lib
     G = 98
-    if mode == "bf16-chained":
-        monkeypatch.setenv("FB_WGRAD_CHAIN", "1")
     eng, _ = _engine(torch.float32 if mode == "fp32" else torch.bfloat16, G)
     P = eng.plan.P
-    assert bool(eng.chain_layers) == (mode == "bf16-chained")
     eng.g[:G].copy_(distinct_rows(G, P, P, 1e-2, 61, "cuda"))
     assert_straddles(eng.g)
     g = eng.g
@@ -450,39 +426,26 @@ def test_engine_fold_over_bucket_ranges(mode, monkeypatch):
     assert all(0 < b < P and b % 4 == 0 for b in bs)
     parts = {b: (sq64_of(0, b), sq64_of(b, P)) for b in bs}
     refs = {c0: running_mean_ref(a0, (g[j] for j in range(G)), c0)[:2] for c0 in (0, 292)}
-    chained = []
-    if eng.chain_layers:
-        for L in eng.chain_layers:
-            lo, hi = L.w_off, L.w_off + L.cout * L.taps * L.cin_real
-            assert lo >= max(bs) and lo % 4 == 0
-            chained.append((lo, hi))
-            eng.gsum[lo:hi] = f32_of(sum(g[j, lo:hi].double() for j in range(G)))
-            L.chain_sq.zero_()
-            L.chain_sq[:G, 0] = f32_of(sq64_of(lo, hi))
-            for c0 in (0, 292):
-                r, bnd = accumulate_sum_ref(a0[lo:hi], eng.gsum[lo:hi], c0, G)
-                refs[c0][0][lo:hi], refs[c0][1][lo:hi] = r, bnd
-        for lo, hi in chained:
-            g[:, lo:hi] = float("nan")
-        eng.chain_on = True
-    try:
-        for b in bs:
-            for c0 in (0, 292):
-                sq_lo, sq_hi = torch.zeros(G, device="cuda"), torch.zeros(G, device="cuda")
-                eng.avg.copy_(a0)
-                eng._fold(g, G, 0, b, c0, sq_lo, eng.mt_ws)
-                eng._fold(g, G, b, P, c0, sq_hi, eng.mt_ws)
-                torch.cuda.synchronize()
-                report(f"Engine._fold {mode} b={b} c0={c0} mean", *within_bound(eng.avg, *refs[c0]))
-                report_rel(f"Engine._fold {mode} b={b} c0={c0} norms of [0,b)", sq_lo, parts[b][0], RED_TOL)
-                report_rel(f"Engine._fold {mode} b={b} c0={c0} norms of [0,b)+[b,P)", sq_lo + sq_hi, parts[b][0] + parts[b][1], RED_TOL)
-                with_sq = eng.avg.clone()
-                eng.avg.copy_(a0)
-                eng._fold(g, G, 0, b, c0, None, eng.mt_ws)
-                eng._fold(g, G, b, P, c0, None, eng.mt_ws)
-                assert torch.equal(eng.avg, with_sq)
-    finally:
-        eng.chain_on = False
+
+    def fold(lo, hi, c0, sq_out):                        # (the call full_gradient makes for the arena range [lo, hi))
+        lib.call("fb_mt_accumulate", eng.avg.data_ptr() + 4 * lo, g.data_ptr() + 4 * lo, P, G, hi - lo, c0, None if sq_out is None else sq_out.data_ptr(),
+                 eng.mt_ws.data_ptr())
+
+    for b in bs:
+        for c0 in (0, 292):
+            sq_lo, sq_hi = torch.zeros(G, device="cuda"), torch.zeros(G, device="cuda")
+            eng.avg.copy_(a0)
+            fold(0, b, c0, sq_lo)
+            fold(b, P, c0, sq_hi)
+            torch.cuda.synchronize()
+            report(f"fold {mode} b={b} c0={c0} mean", *within_bound(eng.avg, *refs[c0]))
+            report_rel(f"fold {mode} b={b} c0={c0} norms of [0,b)", sq_lo, parts[b][0], RED_TOL)
+            report_rel(f"fold {mode} b={b} c0={c0} norms of [0,b)+[b,P)", sq_lo + sq_hi, parts[b][0] + parts[b][1], RED_TOL)
+            with_sq = eng.avg.clone()
+            eng.avg.copy_(a0)
+            fold(0, b, c0, None)
+            fold(b, P, c0, None)
+            assert torch.equal(eng.avg, with_sq)
 
 
 def _fill_state(eng, seed):
