@@ -97,6 +97,8 @@ constexpr Entry kEntries[] = {
     FB_LAUNCH(fb_mt_grad_noise),
     // mini-batch SGD mode
     FB_RECORDABLE(fb_mt_sgd_prep), FB_HOST(fb_mt_sgd_prep_supported), FB_RECORDABLE(fb_mt_sgd_torch),
+    // AdamW (hyp/optim=adam)
+    FB_RECORDABLE(fb_mt_adamw),
 };
 constexpr int kNumEntries = sizeof(kEntries) / sizeof(kEntries[0]);
 constexpr bool launches_take_a_stream() {

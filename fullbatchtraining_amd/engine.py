@@ -1323,6 +1323,38 @@ class Engine:
             self.first_step = first
             self.sgd_step(lr, wd, momentum, dampening, nesterov, grad_clip, lo=self.plan.offsets[name], n=math.prod(self.plan.param_shapes[name]))
 
+    # ---- AdamW (hyp/optim=adam): the state arenas exist only once an Adam update (or a checkpoint of one) asks for them
+    def _adam_arenas(self):
+        if getattr(self, "exp_avg", None) is None:
+            self.exp_avg, self.exp_avg_sq = torch.zeros_like(self.theta), torch.zeros_like(self.theta)
+            self.adam_step = 0
+
+    def adamw_step(self, lr, weight_decay, betas, eps, grad_clip=None, torch_clip=False):
+        """``torch.optim.AdamW.step`` (single-tensor form, amsgrad=False) on the whole arena in one launch, after the clip by the global norm in
+        ``self.norms2[0]``: ``torch_clip=False`` is ``sgd_step``'s form (the clipped gradient is written back to ``self.avg``), ``torch_clip=True``
+        ``clip_grad_norm_``'s (``self.avg`` is left as it is).  The bias corrections are formed here in double from the update count."""
+        self._adam_arenas()
+        self.adam_step += 1
+        b1, b2 = float(betas[0]), float(betas[1])
+        step_size = float(lr) / (1.0 - b1 ** self.adam_step)
+        bc2_sqrt = math.sqrt(1.0 - b2 ** self.adam_step)
+        call("fb_mt_adamw", self.theta.data_ptr(), self.avg.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), self.plan.P,
+             self.norms2.data_ptr(), -1.0 if grad_clip is None else float(grad_clip), 1 if torch_clip else 0, float(lr), float(weight_decay),
+             b1, b2, float(eps), step_size, bc2_sqrt)
+
+    def adam_state(self):
+        """(exp_avg list, exp_avg_sq list, step) in ``model.parameters()`` layout, like ``momentum_state``."""
+        self._adam_arenas()
+        m, v = self.exp_avg.detach().cpu(), self.exp_avg_sq.detach().cpu()
+        return ([self._unflatten(m, name) for name in self.plan.param_names], [self._unflatten(v, name) for name in self.plan.param_names],
+                self.adam_step)
+
+    def load_adam_state(self, exp_avg, exp_avg_sq, step):
+        self._adam_arenas()
+        self.exp_avg.copy_(self.flatten(exp_avg))
+        self.exp_avg_sq.copy_(self.flatten(exp_avg_sq))
+        self.adam_step = int(step)
+
     def apply_clip(self, grad_clip):
         """The clip of ``sgd_step`` applied to ``self.avg`` in place (needed when something acts on the clipped gradient before the
         update: gradient noise, reference training.py:205-215); uses the norm in ``self.norms2[0]``."""

@@ -8,7 +8,7 @@ Mirrors, for ``hyp.train_stochastic=False``:
   _modify_gradient_params    :187-215   (norm bias, global L2 / L-infinity clip, gradient noise)
   evaluate                   :343-388
   get_loss_fn                :391-413   (cross entropy, label smoothing, incorrect-xent: fused into the head kernel)
-  optim_interface            fullbatch/training/optimizers.py:10-93 (Gradient Descent / line_search none; cosine-*, warm-up)
+  optim_interface            fullbatch/training/optimizers.py:10-93 (Gradient Descent / line_search none, Adam = AdamW; cosine-*, warm-up)
   _save_to_checkpoint / _load_from_checkpoint   fullbatch/training/utils.py:43-70 (same 5-list layout)
 
 All arithmetic of a step runs in ``libfbengine.so`` on the GPU; torch optimizers/schedulers are instantiated only as
@@ -75,14 +75,21 @@ class GradualWarmupScheduler(_LRScheduler):
 
 
 def optim_interface(model, cfg_hyp):
-    """Only the branch on the hot path: ``Gradient Descent`` + ``line_search: none`` -> torch.optim.SGD (state container)."""
-    if cfg_hyp.optim.name != "Gradient Descent" or cfg_hyp.optim.get("line_search", "none") != "none":
+    """The branches on the hot path: ``Gradient Descent`` + ``line_search: none`` -> torch.optim.SGD, ``Adam`` -> torch.optim.AdamW (state
+    containers)."""
+    adam = cfg_hyp.optim.name == "Adam"
+    if not adam and (cfg_hyp.optim.name != "Gradient Descent" or cfg_hyp.optim.get("line_search", "none") != "none"):
         raise NotImplementedError(f"optimizer {cfg_hyp.optim.name!r}/{cfg_hyp.optim.get('line_search')!r}: only plain gradient "
-                                  "descent with Nesterov momentum is fused into the engine")
+                                  "descent with Nesterov momentum and AdamW are fused into the engine")
     mod = cfg_hyp.optim_modification.name
     if mod not in ("none", "SAM", "LARS", "LARC"):
         raise ValueError(f"Invalid optim_modification {mod} provided.")
     params = {k: v for k, v in cfg_hyp.optim.items() if k not in ("name", "line_search")}
+    if adam:
+        _check_adam_scope(cfg_hyp)
+        params["betas"] = tuple(params["betas"])
+        optimizer = torch.optim.AdamW(model.parameters(), **params)
+        return optimizer, _scheduler_for(optimizer, cfg_hyp)
     if cfg_hyp.only_linear_layers_weight_decay:      # reference optimizers.py:14-21: one param group per tensor, no decay on biases / gains
         parameter_iterable = []
         for key, value in model.named_parameters():
@@ -98,6 +105,24 @@ def optim_interface(model, cfg_hyp):
     elif mod in ("LARS", "LARC"):
         wrapped = LARS(optimizer, trust_coefficient=cfg_hyp.optim_modification.trust_coefficient, clip=mod == "LARC",
                        eps=cfg_hyp.optim_modification.eps)
+    return wrapped, _scheduler_for(optimizer, cfg_hyp)     # the scheduler drives the wrapped SGD (reference optimizers.py:67 `optimizer.optim`)
+
+
+def _check_adam_scope(cfg_hyp):
+    """What hyp/optim=adam does not cover (the update is ONE fb_mt_adamw launch over the whole arena on one rank)."""
+    if cfg_hyp.optim.get("amsgrad", False):
+        raise NotImplementedError("hyp.optim.amsgrad=True (fb_mt_adamw keeps no running maximum of exp_avg_sq)")
+    if cfg_hyp.optim_modification.name != "none":
+        raise NotImplementedError(f"Adam with optim_modification {cfg_hyp.optim_modification.name!r} (SAM's ascent step and the LARS wrapper are "
+                                  "built around the SGD update)")
+    if cfg_hyp.only_linear_layers_weight_decay:
+        raise NotImplementedError("Adam with only_linear_layers_weight_decay (the AdamW update takes one weight decay for the whole arena)")
+    if torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
+        raise NotImplementedError("Adam on more than one rank (the sharded update would need exp_avg / exp_avg_sq in gather_sharded_state)")
+
+
+def _scheduler_for(optimizer, cfg_hyp):
+    """The lr schedule of reference optimizers.py:69-91 around the (unwrapped) optimizer."""
     sched = cfg_hyp.scheduler
     if sched == "cosine-decay-floored":
         scheduler = torch.optim.lr_scheduler.CosineAnnealingLR(optimizer, cfg_hyp.steps, eta_min=cfg_hyp.optim.lr / 25)
@@ -117,10 +142,10 @@ def optim_interface(model, cfg_hyp):
     if cfg_hyp.warmup > 0:
         scheduler = GradualWarmupScheduler(optimizer, multiplier=1.0, total_epoch=cfg_hyp.warmup, after_scheduler=scheduler)
     # The torch optimizer is a STATE CONTAINER here (param_groups / momentum buffers in the checkpoint layout): the update itself is the engine's
-    # fb_mt_clip_sgd on the arena, so ``optimizer.step()`` is never called -- tell the schedulers that updates do happen, or the first
-    # ``scheduler.step()`` warns "lr_scheduler.step() before optimizer.step()" on every run
+    # fb_mt_clip_sgd / fb_mt_adamw on the arena, so ``optimizer.step()`` is never called -- tell the schedulers that updates do happen, or the
+    # first ``scheduler.step()`` warns "lr_scheduler.step() before optimizer.step()" on every run
     optimizer._opt_called = True
-    return wrapped, scheduler            # the scheduler drives the wrapped SGD (reference optimizers.py:67 `optimizer.optim`)
+    return scheduler
 
 
 class _OptimizerWrapper:
@@ -180,7 +205,16 @@ class LARS(_OptimizerWrapper):
 # checkpoints (reference training/utils.py:43-70)
 # ----------------------------------------------------------------------------------------------------------------------
 def _sync_optimizer_state(engine, model, optimizer):
-    """Expose the arena's momentum as torch SGD state so ``optimizer.state_dict()`` has the reference layout."""
+    """Expose the arena's momentum as torch SGD state (AdamW: step / exp_avg / exp_avg_sq) so ``optimizer.state_dict()`` has the reference
+    layout."""
+    if isinstance(optimizer, torch.optim.AdamW):
+        if getattr(engine, "adam_step", 0) == 0:
+            return
+        exp_avg, exp_avg_sq, step = engine.adam_state()
+        for p, m, v in zip(model.parameters(), exp_avg, exp_avg_sq):     # torch's own state: a float32 scalar step, buffers shaped like p
+            optimizer.state[p] = {"step": torch.tensor(float(step), dtype=torch.float32), "exp_avg": m.to(p.device, p.dtype),
+                                  "exp_avg_sq": v.to(p.device, p.dtype)}
+        return
     if engine.first_step:
         return
     for p, buf in zip(model.parameters(), engine.momentum_state()):
@@ -211,6 +245,9 @@ def _load_from_checkpoint(model, optimizer, scheduler, scaler, counter, max_step
     counter.step = step
     if engine is not None:
         engine.load_from_model(model)
+        states = [optimizer.state[p] for p in model.parameters() if p in optimizer.state]
+        if isinstance(optimizer, torch.optim.AdamW) and len(states) == len(list(model.parameters())) and all("exp_avg" in st for st in states):
+            engine.load_adam_state([st["exp_avg"] for st in states], [st["exp_avg_sq"] for st in states], int(float(states[0]["step"])))
         bufs = [optimizer.state[p].get("momentum_buffer") for p in model.parameters() if p in optimizer.state]
         if len(bufs) == len(list(model.parameters())) and all(b is not None for b in bufs):
             engine.load_momentum(bufs)
@@ -301,6 +338,8 @@ def _check_scope(cfg, branch="full-batch"):
     if bool(hyp.train_stochastic) != (branch == "stochastic"):
         raise NotImplementedError(f"hyp.train_stochastic={bool(hyp.train_stochastic)} does not select the {branch} branch this check was asked about "
                                   "(FullBatchTrainer runs both: it checks the branch the configuration selects)")
+    if hyp.optim.name == "Adam":
+        _check_adam_scope(hyp)
     if hyp.train_stochastic:         # mini-batch SGD mode (reference training.py:241-286)
         if torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
             raise NotImplementedError("hyp.train_stochastic on more than one rank (the reference all-reduces every mini-batch gradient; the engine's "
@@ -442,6 +481,8 @@ class FullBatchTrainer:
         # the multi-process code path (collectives, sharded update); FB_FORCE_DIST=1 takes it with an initialised process group of ONE
         # rank as well, which runs the real RCCL reduce-scatter / all-gather calls on a 1-GPU box (tests/test_gpu_sharded.py)
         self.multi = self.world > 1 or (torch.distributed.is_initialized() and os.environ.get("FB_FORCE_DIST") == "1")
+        if self.multi and cfg.hyp.optim.name == "Adam":
+            raise NotImplementedError("Adam on the multi-process code path (the sharded update would need exp_avg / exp_avg_sq in gather_sharded_state)")
         # a shuffling train loader: the dataset stays resident in dataset order and every step regathers it in the order of a new
         # pass over the loader's batch sampler (reference: `for block, (inputs, labels) in enumerate(trainloader)` every step)
         self.shuffler = trainloader if _is_shuffling(trainloader) else None
@@ -681,9 +722,13 @@ class FullBatchTrainer:
             # ---- the update section: norm, update, compute-dtype copies of the new parameters
             if hyp.grad_clip is not None:        # |avg|^2 of the (regularised) block gradient for the clip
                 lib.call("fb_mt_norms2", eng.avg.data_ptr(), None, eng.plan.P, eng.norms2.data_ptr(), eng.mt_ws.data_ptr())
-            eng.sgd_prep_step(lr, o.weight_decay, o.momentum, o.dampening, o.nesterov, hyp.grad_clip, fused=self.sgd_fused)
-            if not self.sgd_fused:               # the composition: fb_weight_prep per layer (a recorded list)
+            if o.name == "Adam":                 # torch.optim.AdamW after clip_grad_norm_, then the unfused weight copies
+                eng.adamw_step(lr, o.weight_decay, o.betas, o.eps, hyp.grad_clip, torch_clip=True)
                 eng.prep_weights(eng.theta, 1)
+            else:
+                eng.sgd_prep_step(lr, o.weight_decay, o.momentum, o.dampening, o.nesterov, hyp.grad_clip, fused=self.sgd_fused)
+                if not self.sgd_fused:           # the composition: fb_weight_prep per layer (a recorded list)
+                    eng.prep_weights(eng.theta, 1)
             if sections is not None:
                 end = torch.cuda.Event(enable_timing=True)
                 end.record()
@@ -724,7 +769,9 @@ class FullBatchTrainer:
         """Clip + Nesterov SGD on the arena; per-tensor weight decay when the optimizer has one param group per tensor
         (``hyp.only_linear_layers_weight_decay``, reference optimizers.py:14-21)."""
         eng, hyp, o = self.engine, self.cfg.hyp, self.cfg.hyp.optim
-        if hyp.only_linear_layers_weight_decay and not zero_wd:
+        if o.name == "Adam":                     # one fb_mt_adamw launch; the clip is this branch's form and clips eng.avg in place
+            eng.adamw_step(lr, o.weight_decay, o.betas, o.eps, grad_clip)
+        elif hyp.only_linear_layers_weight_decay and not zero_wd:
             wds = [g["weight_decay"] for g in self.optimizer.param_groups]
             eng.sgd_step_per_tensor(lr, wds, o.momentum, o.dampening, o.nesterov, grad_clip)
         else:

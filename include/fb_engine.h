@@ -359,6 +359,18 @@ int fb_mt_sgd_prep(float* theta, const float* grad, float* mom, int64_t n, const
 int32_t fb_mt_sgd_prep_supported(int32_t dtype, int32_t f16x2_planes);
 int fb_mt_sgd_torch(float* theta, const float* grad, float* mom, int64_t n, const float* gnorm2, float grad_clip, float lr,
                     float weight_decay, float momentum, float dampening, int32_t nesterov, int32_t first_step, void* stream);
+/* AdamW (hyp/optim=adam: torch.optim.AdamW, single-tensor form, amsgrad=False; additive, ABI v17) on [0, n) of the pointers given, one launch:
+ *   g = coef grad;  p *= 1 - lr wd;  m = beta1 m + (1 - beta1) g;  v = beta2 v + (1 - beta2) g g;
+ *   p -= step_size m / (sqrt(v) / bc2_sqrt + eps)
+ * step_size = lr / (1 - beta1^t) and bc2_sqrt = sqrt(1 - beta2^t) are formed by the host in double from the update count t (this one included).
+ * The clip reads the device scalar gnorm2[0] (grad_clip < 0: none): torch_clip = 0 is fb_mt_clip_sgd's form (norm > clip: coef = clip / (norm +
+ * 1e-6)) and writes the clipped gradient back to grad; torch_clip = 1 is clip_grad_norm_'s, min(1, clip / (norm + 1e-6)), grad read only.
+ * step_size = 0 leaves theta bit-identical while exp_avg / exp_avg_sq advance.  Any 4-byte aligned offset and any n; 16-byte accesses where the
+ * four operands share their misalignment.  Refused without a launch: null pointers, a clip without gnorm2, a beta outside [0, 1), eps <= 0,
+ * bc2_sqrt <= 0. */
+int fb_mt_adamw(float* theta, float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, const float* gnorm2, float grad_clip,
+                int32_t torch_clip, float lr, float weight_decay, float beta1, float beta2, float eps, float step_size, float bc2_sqrt,
+                void* stream);
 
 #ifdef __cplusplus
 }
