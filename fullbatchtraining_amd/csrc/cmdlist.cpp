@@ -99,6 +99,8 @@ constexpr Entry kEntries[] = {
     FB_RECORDABLE(fb_mt_sgd_prep), FB_HOST(fb_mt_sgd_prep_supported), FB_RECORDABLE(fb_mt_sgd_torch),
     // AdamW (hyp/optim=adam)
     FB_RECORDABLE(fb_mt_adamw),
+    // GD-AGC (hyp/optim=gd_agc)
+    FB_RECORDABLE(fb_mt_agc_sgd),
 };
 constexpr int kNumEntries = sizeof(kEntries) / sizeof(kEntries[0]);
 constexpr bool launches_take_a_stream() {

@@ -196,6 +196,27 @@ class Plan:
         self.fcw_off, self.fcb_off = self.offsets["fc.weight"], self.offsets["fc.bias"]
 
 
+def agc_unit_rows(plan):
+    """Unit table of fb_mt_agc_sgd for a plan's arena: one row [offset, unit_len, n_units, clip_on] per parameter tensor, in arena order.  The
+    units are those of the reference's ``unitwise_norm`` (additional_optimizers/sgd_agc.py:10-27), taken literally: a tensor that squeezes to at
+    most one dimension is summed over ITS axis 0 -- ONE unit if that is where its elements lie (every BatchNorm vector and bias), and one unit
+    per ELEMENT for a shape like [1, 4, 1, 1], whose axis 0 has length 1; otherwise one unit per row of a 2-D tensor and per output channel of a
+    4-D one -- contiguous in the arena, whose convolution weights are stored KRSC.  (Its units of a 3-D tensor, summed over axis 1 only, would
+    not be contiguous: refused.)  ``clip_on`` = 0 for tensors named ``linear*`` (reference optimizers.py:48-49)."""
+    rows = []
+    for name in plan.param_names:
+        shape = plan.param_shapes[name]
+        numel = math.prod(shape)
+        if len(shape) not in (1, 2, 4):
+            raise lib.EngineError(f"{name}: GD-AGC has no contiguous unit norm for a parameter of shape {shape}")
+        if sum(1 for s in shape if s != 1) <= 1:
+            units = numel // shape[0]
+        else:
+            units = shape[0]
+        rows.append([plan.offsets[name], numel // units, units, 0 if name.startswith("linear") else 1])
+    return rows
+
+
 def stem_patches(x_nchw, layer, dtype, aug=None, out=None):
     """[N,C,H,W] fp32 (device) -> [N,Ho,Wo,cin_pad] patches in tap-major (kh,kw,c) order matching the KRSC weights
     (`fb_stem_patches`).  ``aug = (crop_oy, crop_ox, flip, crop_pad, pad_value)``: per-image int8 device tensors for the on-device
@@ -1354,6 +1375,24 @@ class Engine:
         self.exp_avg.copy_(self.flatten(exp_avg))
         self.exp_avg_sq.copy_(self.flatten(exp_avg_sq))
         self.adam_step = int(step)
+
+    # ---- GD-AGC (hyp/optim=gd_agc): the momentum is the arena `mom` of the SGD update (momentum_state / load_momentum as they are)
+    def agc_unit_table(self):
+        """Device unit table of fb_mt_agc_sgd (``agc_unit_rows``).  Built once: the library checks a table per address."""
+        if getattr(self, "_agc_tab", None) is None:
+            self._agc_tab = torch.tensor(agc_unit_rows(self.plan), dtype=torch.int64, device=self.device)
+        return self._agc_tab
+
+    def agc_sgd_step(self, lr, weight_decay, momentum, dampening, nesterov, clipping, eps, grad_clip=None, torch_clip=False):
+        """The reference's ``SGD_AGC.step`` on the whole arena in one launch, after the clip by the global norm in ``self.norms2[0]``:
+        ``torch_clip=False`` is ``sgd_step``'s form (the globally clipped gradient is written back to ``self.avg``), ``torch_clip=True``
+        ``clip_grad_norm_``'s (``self.avg`` is left as it is).  The unit-clipped gradient is never written.  ``clipping=None``: plain SGD."""
+        tab = self.agc_unit_table()
+        call("fb_mt_agc_sgd", self.theta.data_ptr(), self.avg.data_ptr(), self.mom.data_ptr(), self.plan.P, self.norms2.data_ptr(),
+             -1.0 if grad_clip is None else float(grad_clip), 1 if torch_clip else 0, float(lr), float(weight_decay), float(momentum),
+             float(dampening), 1 if nesterov else 0, 1 if self.first_step else 0, -1.0 if clipping is None else float(clipping), float(eps),
+             tab.data_ptr(), tab.shape[0])
+        self.first_step = False
 
     def apply_clip(self, grad_clip):
         """The clip of ``sgd_step`` applied to ``self.avg`` in place (needed when something acts on the clipped gradient before the

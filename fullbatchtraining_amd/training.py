@@ -8,7 +8,7 @@ Mirrors, for ``hyp.train_stochastic=False``:
   _modify_gradient_params    :187-215   (norm bias, global L2 / L-infinity clip, gradient noise)
   evaluate                   :343-388
   get_loss_fn                :391-413   (cross entropy, label smoothing, incorrect-xent: fused into the head kernel)
-  optim_interface            fullbatch/training/optimizers.py:10-93 (Gradient Descent / line_search none, Adam = AdamW; cosine-*, warm-up)
+  optim_interface            fullbatch/training/optimizers.py:10-93 (Gradient Descent / line_search none, Adam = AdamW, GD-AGC; cosine-*, warm-up)
   _save_to_checkpoint / _load_from_checkpoint   fullbatch/training/utils.py:43-70 (same 5-list layout)
 
 All arithmetic of a step runs in ``libfbengine.so`` on the GPU; torch optimizers/schedulers are instantiated only as
@@ -75,12 +75,12 @@ class GradualWarmupScheduler(_LRScheduler):
 
 
 def optim_interface(model, cfg_hyp):
-    """The branches on the hot path: ``Gradient Descent`` + ``line_search: none`` -> torch.optim.SGD, ``Adam`` -> torch.optim.AdamW (state
-    containers)."""
-    adam = cfg_hyp.optim.name == "Adam"
-    if not adam and (cfg_hyp.optim.name != "Gradient Descent" or cfg_hyp.optim.get("line_search", "none") != "none"):
+    """The branches on the hot path: ``Gradient Descent`` + ``line_search: none`` -> torch.optim.SGD, ``Adam`` -> torch.optim.AdamW, ``GD-AGC``
+    -> ``SGD_AGC`` (state containers)."""
+    adam, agc = cfg_hyp.optim.name == "Adam", cfg_hyp.optim.name == "GD-AGC"
+    if not adam and not agc and (cfg_hyp.optim.name != "Gradient Descent" or cfg_hyp.optim.get("line_search", "none") != "none"):
         raise NotImplementedError(f"optimizer {cfg_hyp.optim.name!r}/{cfg_hyp.optim.get('line_search')!r}: only plain gradient "
-                                  "descent with Nesterov momentum and AdamW are fused into the engine")
+                                  "descent with Nesterov momentum, AdamW and GD-AGC are fused into the engine")
     mod = cfg_hyp.optim_modification.name
     if mod not in ("none", "SAM", "LARS", "LARC"):
         raise ValueError(f"Invalid optim_modification {mod} provided.")
@@ -89,6 +89,13 @@ def optim_interface(model, cfg_hyp):
         _check_adam_scope(cfg_hyp)
         params["betas"] = tuple(params["betas"])
         optimizer = torch.optim.AdamW(model.parameters(), **params)
+        return optimizer, _scheduler_for(optimizer, cfg_hyp)
+    if agc:                                          # reference optimizers.py:45-52: a group per tensor, no unit clip for groups named linear*
+        _check_agc_scope(cfg_hyp)
+        optimizer = SGD_AGC(model.named_parameters(), **params)
+        for group in optimizer.param_groups:
+            if group["name"].startswith("linear"):
+                group["clipping"] = None
         return optimizer, _scheduler_for(optimizer, cfg_hyp)
     if cfg_hyp.only_linear_layers_weight_decay:      # reference optimizers.py:14-21: one param group per tensor, no decay on biases / gains
         parameter_iterable = []
@@ -121,6 +128,35 @@ def _check_adam_scope(cfg_hyp):
         raise NotImplementedError("Adam on more than one rank (the sharded update would need exp_avg / exp_avg_sq in gather_sharded_state)")
 
 
+def _check_agc_scope(cfg_hyp):
+    """What hyp/optim=gd_agc does not cover (the update is ONE fb_mt_agc_sgd launch over the whole arena on one rank)."""
+    if cfg_hyp.optim_modification.name != "none":
+        raise NotImplementedError(f"GD-AGC with optim_modification {cfg_hyp.optim_modification.name!r} (SAM's ascent step and the LARS wrapper are "
+                                  "built around the plain SGD update)")
+    if cfg_hyp.only_linear_layers_weight_decay:
+        raise NotImplementedError("GD-AGC with only_linear_layers_weight_decay (the reference selects the tensors by a second regex here; the "
+                                  "fb_mt_agc_sgd launch takes one weight decay for the whole arena)")
+    if torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
+        raise NotImplementedError("GD-AGC on more than one rank (the shard boundaries of the sharded update cut through units)")
+
+
+class SGD_AGC(torch.optim.Optimizer):
+    """State container with the layout of the reference's ``SGD_AGC`` (additional_optimizers/sgd_agc.py): one param group per named tensor
+    carrying ``name``, ``clipping``, ``eps`` and the SGD keys; ``state[p]["momentum_buffer"]``.  It holds no arithmetic: the update is the
+    engine's fb_mt_agc_sgd on the arena."""
+
+    def __init__(self, named_params, lr, momentum=0, dampening=0, weight_decay=0, nesterov=False, clipping=None, eps=1e-3):
+        if lr < 0.0 or momentum < 0.0 or weight_decay < 0.0:
+            raise ValueError(f"Invalid lr / momentum / weight_decay: {lr} / {momentum} / {weight_decay}")
+        if nesterov and (momentum <= 0 or dampening != 0):
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        defaults = dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov, clipping=clipping, eps=eps)
+        super().__init__([{"params": param, "name": name} for name, param in named_params], defaults)
+
+    def step(self, closure=None):
+        raise RuntimeError("SGD_AGC is a state container: the update runs in the engine (Engine.agc_sgd_step)")
+
+
 def _scheduler_for(optimizer, cfg_hyp):
     """The lr schedule of reference optimizers.py:69-91 around the (unwrapped) optimizer."""
     sched = cfg_hyp.scheduler
@@ -142,7 +178,7 @@ def _scheduler_for(optimizer, cfg_hyp):
     if cfg_hyp.warmup > 0:
         scheduler = GradualWarmupScheduler(optimizer, multiplier=1.0, total_epoch=cfg_hyp.warmup, after_scheduler=scheduler)
     # The torch optimizer is a STATE CONTAINER here (param_groups / momentum buffers in the checkpoint layout): the update itself is the engine's
-    # fb_mt_clip_sgd / fb_mt_adamw on the arena, so ``optimizer.step()`` is never called -- tell the schedulers that updates do happen, or the
+    # fb_mt_clip_sgd / fb_mt_adamw / fb_mt_agc_sgd on the arena, so ``optimizer.step()`` is never called -- tell the schedulers that updates do happen, or the
     # first ``scheduler.step()`` warns "lr_scheduler.step() before optimizer.step()" on every run
     optimizer._opt_called = True
     return scheduler
@@ -340,6 +376,8 @@ def _check_scope(cfg, branch="full-batch"):
                                   "(FullBatchTrainer runs both: it checks the branch the configuration selects)")
     if hyp.optim.name == "Adam":
         _check_adam_scope(hyp)
+    if hyp.optim.name == "GD-AGC":
+        _check_agc_scope(hyp)
     if hyp.train_stochastic:         # mini-batch SGD mode (reference training.py:241-286)
         if torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
             raise NotImplementedError("hyp.train_stochastic on more than one rank (the reference all-reduces every mini-batch gradient; the engine's "
@@ -483,6 +521,8 @@ class FullBatchTrainer:
         self.multi = self.world > 1 or (torch.distributed.is_initialized() and os.environ.get("FB_FORCE_DIST") == "1")
         if self.multi and cfg.hyp.optim.name == "Adam":
             raise NotImplementedError("Adam on the multi-process code path (the sharded update would need exp_avg / exp_avg_sq in gather_sharded_state)")
+        if self.multi and cfg.hyp.optim.name == "GD-AGC":
+            raise NotImplementedError("GD-AGC on the multi-process code path (the shard boundaries of the sharded update cut through units)")
         # a shuffling train loader: the dataset stays resident in dataset order and every step regathers it in the order of a new
         # pass over the loader's batch sampler (reference: `for block, (inputs, labels) in enumerate(trainloader)` every step)
         self.shuffler = trainloader if _is_shuffling(trainloader) else None
@@ -725,6 +765,9 @@ class FullBatchTrainer:
             if o.name == "Adam":                 # torch.optim.AdamW after clip_grad_norm_, then the unfused weight copies
                 eng.adamw_step(lr, o.weight_decay, o.betas, o.eps, hyp.grad_clip, torch_clip=True)
                 eng.prep_weights(eng.theta, 1)
+            elif o.name == "GD-AGC":             # SGD_AGC after clip_grad_norm_, then the unfused weight copies
+                eng.agc_sgd_step(lr, o.weight_decay, o.momentum, o.dampening, o.nesterov, o.clipping, o.eps, hyp.grad_clip, torch_clip=True)
+                eng.prep_weights(eng.theta, 1)
             else:
                 eng.sgd_prep_step(lr, o.weight_decay, o.momentum, o.dampening, o.nesterov, hyp.grad_clip, fused=self.sgd_fused)
                 if not self.sgd_fused:           # the composition: fb_weight_prep per layer (a recorded list)
@@ -771,6 +814,8 @@ class FullBatchTrainer:
         eng, hyp, o = self.engine, self.cfg.hyp, self.cfg.hyp.optim
         if o.name == "Adam":                     # one fb_mt_adamw launch; the clip is this branch's form and clips eng.avg in place
             eng.adamw_step(lr, o.weight_decay, o.betas, o.eps, grad_clip)
+        elif o.name == "GD-AGC":                 # one fb_mt_agc_sgd launch; eng.avg keeps the global clip only
+            eng.agc_sgd_step(lr, o.weight_decay, o.momentum, o.dampening, o.nesterov, o.clipping, o.eps, grad_clip)
         elif hyp.only_linear_layers_weight_decay and not zero_wd:
             wds = [g["weight_decay"] for g in self.optimizer.param_groups]
             eng.sgd_step_per_tensor(lr, wds, o.momentum, o.dampening, o.nesterov, grad_clip)

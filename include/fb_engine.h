@@ -371,6 +371,23 @@ int fb_mt_sgd_torch(float* theta, const float* grad, float* mom, int64_t n, cons
 int fb_mt_adamw(float* theta, float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, const float* gnorm2, float grad_clip,
                 int32_t torch_clip, float lr, float weight_decay, float beta1, float beta2, float eps, float step_size, float bc2_sqrt,
                 void* stream);
+/* GD-AGC (hyp/optim=gd_agc: the reference's SGD_AGC, Nesterov SGD with adaptive gradient clipping per output unit; additive, ABI v17), one
+ * launch.  unit_tab: n_rows device rows of four int64 {offset, unit_len, n_units, clip_on}, one per tensor, sorted by offset: the tensor's units
+ * are the n_units consecutive runs of unit_len floats from offset (a KRSC convolution weight: Cout units of taps * Cin; a 1-D tensor: 1 unit).
+ *   g' = coef grad                                   the global clip of fb_mt_clip_sgd (torch_clip = 0: written back to grad) or of
+ *                                                    clip_grad_norm_ (torch_clip = 1: grad read only), as in fb_mt_adamw
+ *   per unit: pn = max(|p_u|, agc_eps), gn = |g'_u|, maxn = pn clipping;  d = gn > maxn ? g' (maxn / max(gn, 1e-6)) : g'
+ *   then fb_mt_clip_sgd's update on d (weight decay, momentum buffer, dampening, Nesterov, first_step).
+ * clipping < 0, or clip_on = 0 in a row: no unit clip, the bits of fb_mt_clip_sgd.  The unit-clipped gradient is never written.  Each unit's
+ * two sums of squares are formed by one owner (a wave up to 1024 floats, a workgroup above) in an order that depends on unit_len alone: the
+ * result does not depend on the grid or on how a table is split over launches.  Units of at most 5120 floats stay in registers between the
+ * norms and the update (every element fetched once); longer ones are read a second time.  Elements of [0, n) in no unit are neither read nor
+ * written.  Any 4-byte aligned pointers; rows need not be 16-byte aligned.  The table is checked once per (address, n_rows, n) (one blocking copy) and again by the kernel.  Refused without a launch:
+ * null pointers (mom may be null with momentum 0), a clip without gnorm2, agc_eps <= 0 with clipping >= 0, more than 1024 rows, a table that is
+ * not sorted, overlaps, leaves [0, n) or has a unit_len or n_units below 1. */
+int fb_mt_agc_sgd(float* theta, float* grad, float* mom, int64_t n, const float* gnorm2, float grad_clip, int32_t torch_clip, float lr,
+                  float weight_decay, float momentum, float dampening, int32_t nesterov, int32_t first_step, float clipping, float agc_eps,
+                  const int64_t* unit_tab, int32_t n_rows, void* stream);
 
 #ifdef __cplusplus
 }
