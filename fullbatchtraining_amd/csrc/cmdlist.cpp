@@ -101,6 +101,8 @@ constexpr Entry kEntries[] = {
     FB_RECORDABLE(fb_mt_adamw),
     // GD-AGC (hyp/optim=gd_agc)
     FB_RECORDABLE(fb_mt_agc_sgd),
+    // FISTA (hyp/optim=fista)
+    FB_RECORDABLE(fb_mt_fista),
 };
 constexpr int kNumEntries = sizeof(kEntries) / sizeof(kEntries[0]);
 constexpr bool launches_take_a_stream() {

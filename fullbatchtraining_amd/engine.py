@@ -16,6 +16,7 @@ import os
 import time
 import warnings
 
+import numpy as np
 import torch
 
 from . import lib
@@ -215,6 +216,31 @@ def agc_unit_rows(plan):
             units = shape[0]
         rows.append([plan.offsets[name], numel // units, units, 0 if name.startswith("linear") else 1])
     return rows
+
+
+def fista_coefficients(tk, fista_mod):
+    """One advance of FISTA's overrelaxation sequence in float32: ``tk' = (p + sqrt(q + r tk^2)) / 2``, ``ak = (tk - 1) / tk'`` with
+    ``fista_mod = (p, q, r)``.  -> ``(tk', ak, 1 + ak)`` as numpy.float32.  From ``tk = 1``: ``ak = 0``.
+
+    Formed with the reference's own expression (additional_optimizers/fista.py:73-76) on a float32 CPU tensor of shape [1], not with numpy:
+    the two agree operation by operation except in ``sqrt``, where torch's CPU kernel is within one unit in the last place of the IEEE result
+    but not always equal to it (sqrt(float32 9.129597663879395) is 3.021522283554077 in torch, 3.0215225219726562 correctly rounded).  That
+    puts a numpy sequence one ulp off the reference's ``tk`` from step 26 on with fista_mod (1/50, 1/10, 4) and from step 141 with (1, 1, 4);
+    on another processor torch's root of float32 4.1 is already one ulp off, at step 1 of the first of these.  The reference is the yardstick,
+    so its arithmetic is the one used: ``tk`` is what the reference forms on this host's CPU, and may differ between hosts by that ulp of the
+    root.  A few tiny host operations per update."""
+    try:
+        mod = [float(v) for v in fista_mod]
+    except (TypeError, ValueError):
+        mod = []
+    if len(mod) != 3 or not all(math.isfinite(v) for v in mod):
+        raise ValueError(f"fista_mod must be three finite numbers (p, q, r), got {fista_mod!r}")
+    p, q, r = mod
+    with torch.no_grad():
+        t = torch.full((1,), float(np.float32(tk)), dtype=torch.float32)
+        t_new = (p + torch.sqrt(q + r * t ** 2)) / 2
+        ak = (t - 1) / t_new
+        return t_new.numpy()[0], ak.numpy()[0], (1 + ak).numpy()[0]
 
 
 def stem_patches(x_nchw, layer, dtype, aug=None, out=None):
@@ -1393,6 +1419,32 @@ class Engine:
              float(dampening), 1 if nesterov else 0, 1 if self.first_step else 0, -1.0 if clipping is None else float(clipping), float(eps),
              tab.data_ptr(), tab.shape[0])
         self.first_step = False
+
+    # ---- FISTA (hyp/optim=fista): the state arena exists only once a FISTA update (or a checkpoint of one) asks for it
+    def _fista_arena(self):
+        if getattr(self, "x_minus", None) is None:
+            self.x_minus = self.theta.detach().clone()       # the reference's x- = param.clone() at first use (never empty: x_minus * 0 must be 0)
+            self.fista_tk = np.float32(1)
+
+    def fista_step(self, lr, fista_mod, grad_clip=None, torch_clip=False):
+        """The reference's ``FISTA.step`` (projection None) on the whole arena in one launch, after the clip by the global norm in
+        ``self.norms2[0]``: ``torch_clip=False`` is ``sgd_step``'s form (the clipped gradient is written back to ``self.avg``), ``torch_clip=True``
+        ``clip_grad_norm_``'s (``self.avg`` is left as it is).  ``tk`` advances here (``fista_coefficients``): one sequence for all tensors."""
+        self._fista_arena()
+        self.fista_tk, ak, one_plus_ak = fista_coefficients(self.fista_tk, fista_mod)
+        call("fb_mt_fista", self.theta.data_ptr(), self.avg.data_ptr(), self.x_minus.data_ptr(), self.plan.P, self.norms2.data_ptr(),
+             -1.0 if grad_clip is None else float(grad_clip), 1 if torch_clip else 0, float(lr), float(ak), float(one_plus_ak))
+
+    def fista_state(self):
+        """(x_minus list in ``model.parameters()`` layout, tk as numpy.float32), like ``adam_state``."""
+        self._fista_arena()
+        x = self.x_minus.detach().cpu()
+        return [self._unflatten(x, name) for name in self.plan.param_names], self.fista_tk
+
+    def load_fista_state(self, x_minus, tk):
+        self._fista_arena()
+        self.x_minus.copy_(self.flatten(x_minus))
+        self.fista_tk = np.float32(tk)
 
     def apply_clip(self, grad_clip):
         """The clip of ``sgd_step`` applied to ``self.avg`` in place (needed when something acts on the clipped gradient before the

@@ -8,7 +8,7 @@ Mirrors, for ``hyp.train_stochastic=False``:
   _modify_gradient_params    :187-215   (norm bias, global L2 / L-infinity clip, gradient noise)
   evaluate                   :343-388
   get_loss_fn                :391-413   (cross entropy, label smoothing, incorrect-xent: fused into the head kernel)
-  optim_interface            fullbatch/training/optimizers.py:10-93 (Gradient Descent / line_search none, Adam = AdamW, GD-AGC; cosine-*, warm-up)
+  optim_interface            fullbatch/training/optimizers.py:10-93 (Gradient Descent / line_search none, Adam = AdamW, GD-AGC, FISTA; cosine-*, warm-up)
   _save_to_checkpoint / _load_from_checkpoint   fullbatch/training/utils.py:43-70 (same 5-list layout)
 
 All arithmetic of a step runs in ``libfbengine.so`` on the GPU; torch optimizers/schedulers are instantiated only as
@@ -16,6 +16,7 @@ All arithmetic of a step runs in ``libfbengine.so`` on the GPU; torch optimizers
 exact layout and the LR sequence is produced by the same torch code the reference calls.
 """
 import logging
+import math
 import os
 import re
 import time
@@ -76,11 +77,11 @@ class GradualWarmupScheduler(_LRScheduler):
 
 def optim_interface(model, cfg_hyp):
     """The branches on the hot path: ``Gradient Descent`` + ``line_search: none`` -> torch.optim.SGD, ``Adam`` -> torch.optim.AdamW, ``GD-AGC``
-    -> ``SGD_AGC`` (state containers)."""
-    adam, agc = cfg_hyp.optim.name == "Adam", cfg_hyp.optim.name == "GD-AGC"
-    if not adam and not agc and (cfg_hyp.optim.name != "Gradient Descent" or cfg_hyp.optim.get("line_search", "none") != "none"):
+    -> ``SGD_AGC``, ``FISTA`` -> ``FISTA`` (state containers)."""
+    adam, agc, fista = cfg_hyp.optim.name == "Adam", cfg_hyp.optim.name == "GD-AGC", cfg_hyp.optim.name == "FISTA"
+    if not adam and not agc and not fista and (cfg_hyp.optim.name != "Gradient Descent" or cfg_hyp.optim.get("line_search", "none") != "none"):
         raise NotImplementedError(f"optimizer {cfg_hyp.optim.name!r}/{cfg_hyp.optim.get('line_search')!r}: only plain gradient "
-                                  "descent with Nesterov momentum, AdamW and GD-AGC are fused into the engine")
+                                  "descent with Nesterov momentum, AdamW, GD-AGC and FISTA are fused into the engine")
     mod = cfg_hyp.optim_modification.name
     if mod not in ("none", "SAM", "LARS", "LARC"):
         raise ValueError(f"Invalid optim_modification {mod} provided.")
@@ -96,6 +97,10 @@ def optim_interface(model, cfg_hyp):
         for group in optimizer.param_groups:
             if group["name"].startswith("linear"):
                 group["clipping"] = None
+        return optimizer, _scheduler_for(optimizer, cfg_hyp)
+    if fista:                                        # reference optimizers.py:43-44
+        _check_fista_scope(cfg_hyp)
+        optimizer = FISTA(model.parameters(), **params)
         return optimizer, _scheduler_for(optimizer, cfg_hyp)
     if cfg_hyp.only_linear_layers_weight_decay:      # reference optimizers.py:14-21: one param group per tensor, no decay on biases / gains
         parameter_iterable = []
@@ -140,6 +145,57 @@ def _check_agc_scope(cfg_hyp):
         raise NotImplementedError("GD-AGC on more than one rank (the shard boundaries of the sharded update cut through units)")
 
 
+FISTA_KEYS = ("name", "lr", "fista_mod", "projection")
+
+
+def _check_fista_scope(cfg_hyp):
+    """What hyp/optim=fista does not cover (the update is ONE fb_mt_fista launch over the whole arena on one rank).  The name alone does not
+    select it: the reference hands every key of the group to ``FISTA.__init__`` and dies with a TypeError on a foreign one, so a group that was
+    composed for another optimizer and renamed is refused here."""
+    keys = set(cfg_hyp.optim.keys())
+    if keys != set(FISTA_KEYS):
+        foreign, missing = sorted(keys - set(FISTA_KEYS)), sorted(set(FISTA_KEYS) - keys)
+        raise NotImplementedError(f"optimizer 'FISTA' on a group that is not FISTA's (foreign keys {foreign}, missing keys {missing}): select the "
+                                  "optimizer with hyp/optim=fista")
+    if cfg_hyp.optim.projection is not None:
+        raise NotImplementedError(f"FISTA with projection {cfg_hyp.optim.projection!r} (the reference takes a function handle, which no preset "
+                                  "can carry; fb_mt_fista applies none)")
+    if cfg_hyp.optim_modification.name != "none":
+        raise NotImplementedError(f"FISTA with optim_modification {cfg_hyp.optim_modification.name!r} (SAM's ascent step and the LARS wrapper are "
+                                  "built around the SGD update)")
+    if cfg_hyp.only_linear_layers_weight_decay:
+        raise NotImplementedError("FISTA with only_linear_layers_weight_decay (FISTA has no weight decay; the fb_mt_fista launch takes one group "
+                                  "for the whole arena)")
+    if torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
+        raise NotImplementedError("FISTA on more than one rank (the sharded update would need x_minus in gather_sharded_state)")
+    _fista_mod(cfg_hyp.optim.fista_mod)
+
+
+def _fista_mod(fista_mod):
+    """``fista_mod`` as a tuple of three floats; ValueError for anything but three finite numbers."""
+    try:
+        mod = tuple(float(v) for v in fista_mod)
+    except (TypeError, ValueError):
+        mod = ()
+    if len(mod) != 3 or not all(math.isfinite(v) for v in mod) or any(isinstance(v, (bool, str)) for v in fista_mod):
+        raise ValueError(f"hyp.optim.fista_mod must be three finite numbers (p, q, r), got {fista_mod!r}")
+    return mod
+
+
+class FISTA(torch.optim.Optimizer):
+    """State container with the layout of the reference's ``FISTA`` (additional_optimizers/fista.py): one param group with ``lr``,
+    ``fista_mod``, ``projection``; ``state[p] = {"x+", "x-", "tk"}``.  It holds no arithmetic: the update is the engine's fb_mt_fista on the
+    arena."""
+
+    def __init__(self, params, projection=None, lr=1e-4, fista_mod=(1.0, 1.0, 4.0)):
+        if not 0.0 <= lr:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        super().__init__(params, dict(lr=lr, fista_mod=fista_mod, projection=projection))
+
+    def step(self, closure=None):
+        raise RuntimeError("FISTA is a state container: the update runs in the engine (Engine.fista_step)")
+
+
 class SGD_AGC(torch.optim.Optimizer):
     """State container with the layout of the reference's ``SGD_AGC`` (additional_optimizers/sgd_agc.py): one param group per named tensor
     carrying ``name``, ``clipping``, ``eps`` and the SGD keys; ``state[p]["momentum_buffer"]``.  It holds no arithmetic: the update is the
@@ -178,7 +234,7 @@ def _scheduler_for(optimizer, cfg_hyp):
     if cfg_hyp.warmup > 0:
         scheduler = GradualWarmupScheduler(optimizer, multiplier=1.0, total_epoch=cfg_hyp.warmup, after_scheduler=scheduler)
     # The torch optimizer is a STATE CONTAINER here (param_groups / momentum buffers in the checkpoint layout): the update itself is the engine's
-    # fb_mt_clip_sgd / fb_mt_adamw / fb_mt_agc_sgd on the arena, so ``optimizer.step()`` is never called -- tell the schedulers that updates do happen, or the
+    # fb_mt_clip_sgd / fb_mt_adamw / fb_mt_agc_sgd / fb_mt_fista on the arena, so ``optimizer.step()`` is never called -- tell the schedulers that updates do happen, or the
     # first ``scheduler.step()`` warns "lr_scheduler.step() before optimizer.step()" on every run
     optimizer._opt_called = True
     return scheduler
@@ -241,7 +297,7 @@ class LARS(_OptimizerWrapper):
 # checkpoints (reference training/utils.py:43-70)
 # ----------------------------------------------------------------------------------------------------------------------
 def _sync_optimizer_state(engine, model, optimizer):
-    """Expose the arena's momentum as torch SGD state (AdamW: step / exp_avg / exp_avg_sq) so ``optimizer.state_dict()`` has the reference
+    """Expose the arena's momentum as torch SGD state (AdamW: step / exp_avg / exp_avg_sq; FISTA: x+ / x- / tk) so ``optimizer.state_dict()`` has the reference
     layout."""
     if isinstance(optimizer, torch.optim.AdamW):
         if getattr(engine, "adam_step", 0) == 0:
@@ -250,6 +306,14 @@ def _sync_optimizer_state(engine, model, optimizer):
         for p, m, v in zip(model.parameters(), exp_avg, exp_avg_sq):     # torch's own state: a float32 scalar step, buffers shaped like p
             optimizer.state[p] = {"step": torch.tensor(float(step), dtype=torch.float32), "exp_avg": m.to(p.device, p.dtype),
                                   "exp_avg_sq": v.to(p.device, p.dtype)}
+        return
+    if isinstance(optimizer, FISTA):
+        if getattr(engine, "x_minus", None) is None:
+            return
+        x_minus, tk = engine.fista_state()
+        for p, x in zip(model.parameters(), x_minus):   # the reference's own state: after a step x+ holds the values of x-; tk a float32 tensor [1]
+            x = x.to(p.device, p.dtype)
+            optimizer.state[p] = {"x+": x.clone(), "x-": x, "tk": torch.full((1,), float(tk), dtype=torch.float32, device=p.device)}
         return
     if engine.first_step:
         return
@@ -284,6 +348,8 @@ def _load_from_checkpoint(model, optimizer, scheduler, scaler, counter, max_step
         states = [optimizer.state[p] for p in model.parameters() if p in optimizer.state]
         if isinstance(optimizer, torch.optim.AdamW) and len(states) == len(list(model.parameters())) and all("exp_avg" in st for st in states):
             engine.load_adam_state([st["exp_avg"] for st in states], [st["exp_avg_sq"] for st in states], int(float(states[0]["step"])))
+        if isinstance(optimizer, FISTA) and len(states) == len(list(model.parameters())) and all("x-" in st for st in states):
+            engine.load_fista_state([st["x-"] for st in states], np.float32(states[0]["tk"].detach().cpu().numpy().reshape(-1)[0]))
         bufs = [optimizer.state[p].get("momentum_buffer") for p in model.parameters() if p in optimizer.state]
         if len(bufs) == len(list(model.parameters())) and all(b is not None for b in bufs):
             engine.load_momentum(bufs)
@@ -378,6 +444,8 @@ def _check_scope(cfg, branch="full-batch"):
         _check_adam_scope(hyp)
     if hyp.optim.name == "GD-AGC":
         _check_agc_scope(hyp)
+    if hyp.optim.name == "FISTA":
+        _check_fista_scope(hyp)
     if hyp.train_stochastic:         # mini-batch SGD mode (reference training.py:241-286)
         if torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
             raise NotImplementedError("hyp.train_stochastic on more than one rank (the reference all-reduces every mini-batch gradient; the engine's "
@@ -523,6 +591,8 @@ class FullBatchTrainer:
             raise NotImplementedError("Adam on the multi-process code path (the sharded update would need exp_avg / exp_avg_sq in gather_sharded_state)")
         if self.multi and cfg.hyp.optim.name == "GD-AGC":
             raise NotImplementedError("GD-AGC on the multi-process code path (the shard boundaries of the sharded update cut through units)")
+        if self.multi and cfg.hyp.optim.name == "FISTA":
+            raise NotImplementedError("FISTA on the multi-process code path (the sharded update would need x_minus in gather_sharded_state)")
         # a shuffling train loader: the dataset stays resident in dataset order and every step regathers it in the order of a new
         # pass over the loader's batch sampler (reference: `for block, (inputs, labels) in enumerate(trainloader)` every step)
         self.shuffler = trainloader if _is_shuffling(trainloader) else None
@@ -768,6 +838,9 @@ class FullBatchTrainer:
             elif o.name == "GD-AGC":             # SGD_AGC after clip_grad_norm_, then the unfused weight copies
                 eng.agc_sgd_step(lr, o.weight_decay, o.momentum, o.dampening, o.nesterov, o.clipping, o.eps, hyp.grad_clip, torch_clip=True)
                 eng.prep_weights(eng.theta, 1)
+            elif o.name == "FISTA":              # FISTA after clip_grad_norm_, then the unfused weight copies
+                eng.fista_step(lr, o.fista_mod, hyp.grad_clip, torch_clip=True)
+                eng.prep_weights(eng.theta, 1)
             else:
                 eng.sgd_prep_step(lr, o.weight_decay, o.momentum, o.dampening, o.nesterov, hyp.grad_clip, fused=self.sgd_fused)
                 if not self.sgd_fused:           # the composition: fb_weight_prep per layer (a recorded list)
@@ -816,6 +889,8 @@ class FullBatchTrainer:
             eng.adamw_step(lr, o.weight_decay, o.betas, o.eps, grad_clip)
         elif o.name == "GD-AGC":                 # one fb_mt_agc_sgd launch; eng.avg keeps the global clip only
             eng.agc_sgd_step(lr, o.weight_decay, o.momentum, o.dampening, o.nesterov, o.clipping, o.eps, grad_clip)
+        elif o.name == "FISTA":                  # one fb_mt_fista launch; the clip is this branch's form and clips eng.avg in place
+            eng.fista_step(lr, o.fista_mod, grad_clip)
         elif hyp.only_linear_layers_weight_decay and not zero_wd:
             wds = [g["weight_decay"] for g in self.optimizer.param_groups]
             eng.sgd_step_per_tensor(lr, wds, o.momentum, o.dampening, o.nesterov, grad_clip)

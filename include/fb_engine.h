@@ -388,6 +388,17 @@ int fb_mt_adamw(float* theta, float* grad, float* exp_avg, float* exp_avg_sq, in
 int fb_mt_agc_sgd(float* theta, float* grad, float* mom, int64_t n, const float* gnorm2, float grad_clip, int32_t torch_clip, float lr,
                   float weight_decay, float momentum, float dampening, int32_t nesterov, int32_t first_step, float clipping, float agc_eps,
                   const int64_t* unit_tab, int32_t n_rows, void* stream);
+/* FISTA (hyp/optim=fista: the reference's FISTA, Nesterov-accelerated gradient descent with the explicit t_k sequence, projection None;
+ * additive, ABI v17) on [0, n) of the pointers given, one launch.  Every operation rounded on its own, as the reference's tensor operations:
+ *   g = coef grad;  xp = theta - g lr;  theta = xp one_plus_ak - x_minus ak;  x_minus = xp
+ * ak = (tk - 1) / tk' with tk' = (p + sqrt(q + r tk^2)) / 2 and one_plus_ak = 1 + ak are formed by the host in float32 (the same for every
+ * tensor); the first step has ak = 0 and leaves theta = xp for a finite x_minus.  The clip reads the device scalar gnorm2[0] (grad_clip < 0:
+ * none): torch_clip = 0 is fb_mt_clip_sgd's form (norm > clip: coef = clip / (norm + 1e-6)) and writes the clipped gradient back to grad;
+ * torch_clip = 1 is clip_grad_norm_'s, min(1, clip / (norm + 1e-6)), grad read only.  Any 4-byte aligned offset and any n; 16-byte accesses
+ * where the three operands share their misalignment.  Refused without a launch: null pointers, n < 0, a clip without gnorm2, lr negative or
+ * not finite, ak or one_plus_ak not finite. */
+int fb_mt_fista(float* theta, float* grad, float* x_minus, int64_t n, const float* gnorm2, float grad_clip, int32_t torch_clip, float lr, float ak,
+                float one_plus_ak, void* stream);
 
 #ifdef __cplusplus
 }
