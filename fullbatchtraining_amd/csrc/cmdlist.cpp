@@ -103,6 +103,8 @@ constexpr Entry kEntries[] = {
     FB_RECORDABLE(fb_mt_agc_sgd),
     // FISTA (hyp/optim=fista)
     FB_RECORDABLE(fb_mt_fista),
+    // strong-Wolfe line search (hyp.optim.line_search=wolfe)
+    FB_RECORDABLE(fb_mt_wolfe_direction), FB_RECORDABLE(fb_mt_wolfe_trial), FB_RECORDABLE(fb_mt_wolfe_phi_grad),
 };
 constexpr int kNumEntries = sizeof(kEntries) / sizeof(kEntries[0]);
 constexpr bool launches_take_a_stream() {
@@ -168,6 +170,8 @@ extern "C" int32_t fb_abi_constant(const char* name) {
     if (strcmp(name, "FB_MT_BLOCKS") == 0) return FB_MT_BLOCKS;
     if (strcmp(name, "FB_PROF_CLASSES") == 0) return FB_PROF_CLASSES;
     if (strcmp(name, "FB_PROF_INFO") == 0) return FB_PROF_INFO;
+    if (strcmp(name, "FB_WOLFE_VEC") == 0) return FB_WOLFE_VEC;
+    if (strcmp(name, "FB_WOLFE_BLOCK") == 0) return FB_WOLFE_BLOCK;
     return -1;
 }
 

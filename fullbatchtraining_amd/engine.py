@@ -1446,6 +1446,33 @@ class Engine:
         self.x_minus.copy_(self.flatten(x_minus))
         self.fista_tk = np.float32(tk)
 
+    # ---- strong-Wolfe line search (hyp.optim.line_search=wolfe): the two arenas exist only once a Wolfe step asks for them
+    def _wolfe_arena(self):
+        if getattr(self, "wolfe_p", None) is None:
+            self.wolfe_p, self.wolfe_theta0 = torch.zeros_like(self.theta), torch.zeros_like(self.theta)
+            self.wolfe_out = torch.zeros(2, device=self.device, dtype=torch.float32)       # [sum d p of the direction, phi'(alpha) of the last trial]
+
+    def wolfe_direction(self, weight_decay, momentum, dampening, nesterov):
+        """``_save_initial_state`` + ``_find_descent_direction`` of the reference's WolfeGradientDescent in one pass: from ``self.theta`` and the
+        (clipped) gradient in ``self.avg`` the search direction ``self.wolfe_p``, the snapshot ``self.wolfe_theta0`` and the momentum update
+        (the bits ``sgd_step`` would write without a clip); ``self.wolfe_out[0]`` = phi'(0) = sum d p, a device scalar."""
+        self._wolfe_arena()
+        call("fb_mt_wolfe_direction", self.theta.data_ptr(), self.avg.data_ptr(), self.mom.data_ptr(), self.wolfe_p.data_ptr(),
+             self.wolfe_theta0.data_ptr(), self.plan.P, float(weight_decay), float(momentum), float(dampening), 1 if nesterov else 0,
+             1 if self.first_step else 0, self.wolfe_out.data_ptr(), self.mt_ws.data_ptr())
+        if momentum != 0:
+            self.first_step = False
+
+    def wolfe_trial(self, lr, alpha):
+        """``_attempt_step``: theta = theta0 + (lr alpha) p.  The step is formed in double and cast to float32 once, as torch does with the
+        ``alpha=`` scalar of ``_foreach_add_``."""
+        call("fb_mt_wolfe_trial", self.theta.data_ptr(), self.wolfe_theta0.data_ptr(), self.wolfe_p.data_ptr(), self.plan.P, float(lr) * float(alpha))
+
+    def wolfe_phi_grad(self, weight_decay):
+        """``_get_phi_grad``: ``self.wolfe_out[1]`` = phi'(alpha) = sum (avg + wd theta) p at the current trial point, a device scalar."""
+        call("fb_mt_wolfe_phi_grad", self.theta.data_ptr(), self.avg.data_ptr(), self.wolfe_p.data_ptr(), self.plan.P, float(weight_decay),
+             self.wolfe_out.data_ptr() + 4, self.mt_ws.data_ptr())
+
     def apply_clip(self, grad_clip):
         """The clip of ``sgd_step`` applied to ``self.avg`` in place (needed when something acts on the clipped gradient before the
         update: gradient noise, reference training.py:205-215); uses the norm in ``self.norms2[0]``."""

@@ -8,7 +8,7 @@ Mirrors, for ``hyp.train_stochastic=False``:
   _modify_gradient_params    :187-215   (norm bias, global L2 / L-infinity clip, gradient noise)
   evaluate                   :343-388
   get_loss_fn                :391-413   (cross entropy, label smoothing, incorrect-xent: fused into the head kernel)
-  optim_interface            fullbatch/training/optimizers.py:10-93 (Gradient Descent / line_search none, Adam = AdamW, GD-AGC, FISTA; cosine-*, warm-up)
+  optim_interface            fullbatch/training/optimizers.py:10-93 (Gradient Descent / line_search none or wolfe, Adam = AdamW, GD-AGC, FISTA; cosine-*, warm-up)
   _save_to_checkpoint / _load_from_checkpoint   fullbatch/training/utils.py:43-70 (same 5-list layout)
 
 All arithmetic of a step runs in ``libfbengine.so`` on the GPU; torch optimizers/schedulers are instantiated only as
@@ -76,12 +76,21 @@ class GradualWarmupScheduler(_LRScheduler):
 
 
 def optim_interface(model, cfg_hyp):
-    """The branches on the hot path: ``Gradient Descent`` + ``line_search: none`` -> torch.optim.SGD, ``Adam`` -> torch.optim.AdamW, ``GD-AGC``
-    -> ``SGD_AGC``, ``FISTA`` -> ``FISTA`` (state containers)."""
+    """The branches on the hot path: ``Gradient Descent`` + ``line_search: none`` -> torch.optim.SGD, ``line_search: wolfe`` ->
+    ``WolfeGradientDescent``, ``Adam`` -> torch.optim.AdamW, ``GD-AGC`` -> ``SGD_AGC``, ``FISTA`` -> ``FISTA`` (state containers)."""
     adam, agc, fista = cfg_hyp.optim.name == "Adam", cfg_hyp.optim.name == "GD-AGC", cfg_hyp.optim.name == "FISTA"
+    wolfe = cfg_hyp.optim.name == "Gradient Descent" and cfg_hyp.optim.get("line_search", "none") == "wolfe"
+    if wolfe:                                        # reference optimizers.py:29-30
+        _check_wolfe_scope(cfg_hyp)
+        optimizer = WolfeGradientDescent(model.parameters(), **{k: v for k, v in cfg_hyp.optim.items() if k not in ("name", "line_search")})
+        return optimizer, _scheduler_for(optimizer, cfg_hyp)
+    if cfg_hyp.optim.name == "Gradient Descent" and cfg_hyp.optim.get("line_search", "none") in ("non-monotone", "restarting"):
+        raise NotImplementedError(f"line_search {cfg_hyp.optim.line_search!r}: of the reference's three line searches only the strong-Wolfe search "
+                                  "(line_search=wolfe) runs on the engine; the non-monotone and the restarting search are its follow-ups (both "
+                                  "repeat torch.optim.SGD.step from a saved state, which needs a momentum snapshot next to theta0)")
     if not adam and not agc and not fista and (cfg_hyp.optim.name != "Gradient Descent" or cfg_hyp.optim.get("line_search", "none") != "none"):
         raise NotImplementedError(f"optimizer {cfg_hyp.optim.name!r}/{cfg_hyp.optim.get('line_search')!r}: only plain gradient "
-                                  "descent with Nesterov momentum, AdamW, GD-AGC and FISTA are fused into the engine")
+                                  "descent with Nesterov momentum (line_search none or wolfe), AdamW, GD-AGC and FISTA are fused into the engine")
     mod = cfg_hyp.optim_modification.name
     if mod not in ("none", "SAM", "LARS", "LARC"):
         raise ValueError(f"Invalid optim_modification {mod} provided.")
@@ -194,6 +203,145 @@ class FISTA(torch.optim.Optimizer):
 
     def step(self, closure=None):
         raise RuntimeError("FISTA is a state container: the update runs in the engine (Engine.fista_step)")
+
+
+WOLFE_DEFAULTS = dict(c1=1e-4, c2=0.9, alpha_max=10.0, max_iter=10)      # WolfeGradientDescent.__init__ (the reference's gd.yaml carries none of them)
+
+
+def wolfe_constants(cfg_optim):
+    """(c1, c2, alpha_max, max_iter) of a ``Gradient Descent`` group: the group's own values where it has them (``+hyp.optim.c1=...``), the
+    reference constructor's defaults otherwise."""
+    return tuple(cfg_optim.get(k, v) for k, v in WOLFE_DEFAULTS.items())
+
+
+def _check_wolfe_scope(cfg_hyp):
+    """What hyp.optim.line_search=wolfe does not cover (the search runs on the whole arena of one rank, around the full-batch closure)."""
+    if cfg_hyp.train_stochastic:
+        raise NotImplementedError("line_search=wolfe with hyp.train_stochastic (the reference calls optimizer.step() without a closure in the "
+                                  "mini-batch branch, training.py:274, and dies in WolfeGradientDescent.step)")
+    if cfg_hyp.optim_modification.name != "none":
+        raise NotImplementedError(f"line_search=wolfe with optim_modification {cfg_hyp.optim_modification.name!r} (SAM's two closures and the LARS "
+                                  "wrapper are built around one SGD update per step, not around a search that evaluates the closure itself)")
+    if cfg_hyp.only_linear_layers_weight_decay:
+        raise NotImplementedError("line_search=wolfe with only_linear_layers_weight_decay (fb_mt_wolfe_direction and fb_mt_wolfe_phi_grad take one "
+                                  "weight decay for the whole arena)")
+    if torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
+        raise NotImplementedError("line_search=wolfe on more than one rank (every evaluation would need the exchanged gradient whole on every rank "
+                                  "and one agreed phi'; the sharded update has neither)")
+
+
+class WolfeGradientDescent(torch.optim.Optimizer):
+    """State container with the layout of the reference's ``WolfeGradientDescent`` (additional_optimizers/sgd_linesearch.py:183-203): one param
+    group with the SGD keys and ``c1``, ``c2``, ``alpha_max``, ``max_iter``; ``state[p]["momentum_buffer"]`` and the bare key ``state["alpha"]``
+    (the step length the last search returned).  It holds no arithmetic: direction, trial points and phi' are the engine's fb_mt_wolfe_* on the
+    arena, the search is ``WolfeSearch``."""
+
+    def __init__(self, params, lr=0.1, momentum=0, dampening=0, weight_decay=0, nesterov=False, c1=1e-4, c2=0.9, alpha_max=10.0, max_iter=10):
+        if lr < 0.0:
+            raise ValueError("Invalid learning rate: {}".format(lr))
+        if momentum < 0.0:
+            raise ValueError("Invalid momentum value: {}".format(momentum))
+        if weight_decay < 0.0:
+            raise ValueError("Invalid weight_decay value: {}".format(weight_decay))
+        if nesterov and (momentum <= 0 or dampening != 0):
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        super().__init__(params, dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov, c1=c1, c2=c2,
+                                      alpha_max=alpha_max, max_iter=max_iter))
+
+    def step(self, closure=None):
+        raise RuntimeError("WolfeGradientDescent is a state container: the step runs in FullBatchTrainer.step (WolfeSearch on the engine)")
+
+
+class WolfeSearch:
+    """The control flow of ``WolfeGradientDescent.step`` / ``_zoom`` / ``_interpolate`` (sgd_linesearch.py:303-381) on Python floats: the
+    reference's expressions in the reference's order, its look-up table (a ``defaultdict(dict)`` keyed by alpha, so an alpha that was seen is not
+    evaluated again), its exits -- and its quirks: ``prev_loss`` is never updated, a zoom that runs out of rounds returns an alpha it never
+    evaluated, ``math.sqrt`` of a negative discriminant raises ValueError.  It sees the problem only through ``evaluate(alpha) -> (loss,
+    phi_grad)``: the parameters are left wherever the last evaluation put them.
+
+    After ``search``: ``evaluated`` (every alpha handed to ``evaluate``, in order), ``trace`` (every inequality decided, as
+    ``(name, alpha, left, right)``), ``exit`` (which way the outer loop ended), ``zoom_exit`` (which way the zoom ended, if there was one) and
+    ``table_hits`` (how often the table spared an evaluation)."""
+
+    def __init__(self, c1=1e-4, c2=0.9, alpha_max=10.0, max_iter=10):
+        self.c1, self.c2, self.alpha_max, self.max_iter = c1, c2, alpha_max, max_iter
+        self.evaluated, self.trace, self.exit, self.zoom_exit, self.table_hits = [], [], None, None, 0
+
+    def _evaluate_phi(self, alpha, evaluate, phi):
+        if alpha not in phi:
+            loss, phi_grad = evaluate(alpha)
+            self.evaluated.append(alpha)
+            phi[alpha] = dict(val=loss, grad=phi_grad)
+        else:
+            self.table_hits += 1
+
+    def search(self, loss0, phi_grad0, evaluate):
+        """``loss0 = phi(0)``, ``phi_grad0 = phi'(0)`` -> the alpha the reference stores in ``state['alpha']``."""
+        self.evaluated, self.trace, self.exit, self.zoom_exit, self.table_hits = [], [], "max_iter", None, 0
+        alpha = 1.0
+        phi = defaultdict(dict)
+        phi[0] = dict(val=loss0, grad=phi_grad0)
+        prev_loss = float("inf")
+        prev_alpha = 0
+        for iteration in range(self.max_iter):
+            self._evaluate_phi(alpha, evaluate, phi)
+            sufficient_loss = phi[0]["val"] + self.c1 * alpha * phi[0]["grad"]
+            self.trace.append(("decrease", alpha, phi[alpha]["val"], sufficient_loss))
+            if (phi[alpha]["val"] > sufficient_loss) or (phi[alpha]["val"] > prev_loss):
+                alpha = self._zoom(prev_alpha, alpha, evaluate, phi)
+                self.exit = "zoom-1"
+                break
+            self.trace.append(("curvature", alpha, abs(phi[alpha]["grad"]), -self.c2 * phi[0]["grad"]))
+            if abs(phi[alpha]["grad"]) <= -self.c2 * phi[0]["grad"]:
+                self.exit = "accepted"
+                break
+            self.trace.append(("sign", alpha, phi[alpha]["grad"], 0.0))
+            if phi[alpha]["grad"] >= 0:
+                alpha = self._zoom(alpha, prev_alpha, evaluate, phi)
+                self.exit = "zoom-2"
+                break
+            prev_alpha = alpha
+            alpha = min(alpha * 2.5, self.alpha_max)
+            if alpha == self.alpha_max:
+                self.exit = "alpha_max"
+                break
+        return alpha
+
+    def _zoom(self, alpha_low, alpha_high, evaluate, phi):
+        for iteration in range(self.max_iter):
+            if abs(alpha_low - alpha_high) < 1e-4:
+                self.zoom_exit = "interval"
+                return alpha_low
+            alpha = self._interpolate(alpha_low, alpha_high, phi)
+            self._evaluate_phi(alpha, evaluate, phi)
+            sufficient_loss = phi[0]["val"] + self.c1 * alpha * phi[0]["grad"]
+            self.trace.append(("zoom-decrease", alpha, phi[alpha]["val"], sufficient_loss))
+            self.trace.append(("zoom-low", alpha, phi[alpha]["val"], phi[alpha_low]["val"]))
+            if (phi[alpha]["val"] > sufficient_loss) or (phi[alpha]["val"] > phi[alpha_low]["val"]):
+                alpha_high = alpha
+            else:
+                self.trace.append(("zoom-curvature", alpha, phi[alpha]["grad"], -self.c2 * phi[0]["grad"]))
+                if (phi[alpha]["grad"]) <= -self.c2 * phi[0]["grad"]:
+                    self.zoom_exit = "curvature"
+                    return alpha
+                self.trace.append(("zoom-sign", alpha, phi[alpha]["grad"] * (alpha_high - alpha_low), 0.0))
+                if phi[alpha]["grad"] * (alpha_high - alpha_low) >= 0:
+                    alpha_high = alpha_low
+                alpha_low = alpha
+        self.zoom_exit = "exhausted"
+        return self._interpolate(alpha_low, alpha_high, phi)
+
+    @staticmethod
+    def _interpolate(alpha1, alpha2, phi):
+        """Cubic interpolation as in Nocedal and Wright."""
+        if alpha1 == alpha2:
+            return alpha1
+        quotient = (phi[alpha1]["val"] - phi[alpha2]["val"]) / (alpha1 - alpha2)
+        d_1 = phi[alpha1]["grad"] + phi[alpha2]["grad"] - 3 * quotient
+        d_2 = math.copysign(1.0, alpha2 - alpha1) * math.sqrt(d_1**2 - phi[alpha1]["grad"] * phi[alpha2]["grad"])
+        update_nom = phi[alpha2]["grad"] + d_2 - d_1
+        update_denom = phi[alpha2]["grad"] - phi[alpha1]["grad"] + 2 * d_2
+        return alpha2 - (alpha2 - alpha1) * update_nom / update_denom
 
 
 class SGD_AGC(torch.optim.Optimizer):
@@ -446,6 +594,8 @@ def _check_scope(cfg, branch="full-batch"):
         _check_agc_scope(hyp)
     if hyp.optim.name == "FISTA":
         _check_fista_scope(hyp)
+    if hyp.optim.name == "Gradient Descent" and hyp.optim.get("line_search", "none") == "wolfe":
+        _check_wolfe_scope(hyp)
     if hyp.train_stochastic:         # mini-batch SGD mode (reference training.py:241-286)
         if torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
             raise NotImplementedError("hyp.train_stochastic on more than one rank (the reference all-reduces every mini-batch gradient; the engine's "
@@ -593,6 +743,9 @@ class FullBatchTrainer:
             raise NotImplementedError("GD-AGC on the multi-process code path (the shard boundaries of the sharded update cut through units)")
         if self.multi and cfg.hyp.optim.name == "FISTA":
             raise NotImplementedError("FISTA on the multi-process code path (the sharded update would need x_minus in gather_sharded_state)")
+        if self.multi and cfg.hyp.optim.name == "Gradient Descent" and cfg.hyp.optim.get("line_search", "none") == "wolfe":
+            raise NotImplementedError("line_search=wolfe on the multi-process code path (every evaluation would need the exchanged gradient whole "
+                                      "on every rank and one agreed phi'; the sharded update has neither)")
         # a shuffling train loader: the dataset stays resident in dataset order and every step regathers it in the order of a new
         # pass over the loader's batch sampler (reference: `for block, (inputs, labels) in enumerate(trainloader)` every step)
         self.shuffler = trainloader if _is_shuffling(trainloader) else None
@@ -784,6 +937,10 @@ class FullBatchTrainer:
                 return norms
 
             clip = None if noisy else hyp.grad_clip          # (already applied in place where noise follows it)
+            if o.name == "Gradient Descent" and o.get("line_search", "none") == "wolfe":
+                self._wolfe_step(closure, modify, clip, lr, train_time, (loss_k, correct_k, sq_k))
+                self.scheduler.step()
+                return
             norms = modify()
             if mod == "SAM":                     # sam.py:84-92: closure, first_step, closure, second_step; stats are recorded twice
                 self._record_stats(loss_k, correct_k, sq_k, norms, lr, train_time)
@@ -804,6 +961,34 @@ class FullBatchTrainer:
             return
         self._record_stats(loss_k, correct_k, sq_k, eng.norms2, lr, train_time)
         self.scheduler.step()
+
+    def _wolfe_step(self, closure, modify, clip, lr, train_time, first):
+        """``WolfeGradientDescent.step(closure)`` (sgd_linesearch.py:285-345).  ``first``: the closure's result at theta0, already evaluated.
+        Every evaluation is closure + ``_modify_gradient_params`` with the clip applied IN PLACE (the direction and every phi' use the clipped
+        gradient), one statistics record, and ONE read-back that carries the record, phi'(0) and phi'(alpha) together: the search cannot go on
+        without the loss and phi', so that wait per evaluation is inherent.  The loss the search compares is the record's ``train_loss``.  No final
+        step: the parameters stay at the last evaluated trial point."""
+        eng, o = self.engine, self.cfg.hyp.optim
+
+        def finish(result, slot):
+            norms = modify()
+            if clip is not None:
+                eng.apply_clip(clip)
+            if slot == 0:
+                eng.wolfe_direction(o.weight_decay, o.momentum, o.dampening, o.nesterov)
+            else:
+                eng.wolfe_phi_grad(o.weight_decay)
+            self._record_stats(*result, norms, lr, train_time, extra=eng.wolfe_out)
+            self.flush_stats()
+            return self.stats.raw("train_loss")[-1], self._extra[slot]
+
+        def evaluate(alpha):
+            eng.wolfe_trial(lr, alpha)
+            return finish(closure(), 1)
+
+        loss0, phi_grad0 = finish(first, 0)
+        self.wolfe = WolfeSearch(*wolfe_constants(o))
+        self.optimizer.state["alpha"] = self.wolfe.search(loss0, phi_grad0, evaluate)
 
     def _sgd_epoch(self, lr, train_time):
         """One "step" of the stochastic branch = one epoch (reference training.py:241-286): per block of the loader the block gradient as one
@@ -927,9 +1112,10 @@ class FullBatchTrainer:
             fl = (torch.rand(self._n_total, generator=gen) < a["flip_p"]).to(torch.int8)[lo:lo + n].to(self.device)
         self._gather_patches(self.images, aug=(oy, ox, fl, a["crop_pad"], a["pad_value"]))
 
-    def _record_stats(self, loss_k, correct_k, sq_k, norms2, lr, train_time):
+    def _record_stats(self, loss_k, correct_k, sq_k, norms2, lr, train_time, extra=None):
         """Queue the read-back of one closure's statistics (per-chunk losses / hits / squared gradient norms, the two global norms, the
-        pre-pass norm, the per-chunk clip count) and finish the records of earlier closures, whose kernels are long done."""
+        pre-pass norm, the per-chunk clip count) and finish the records of earlier closures, whose kernels are long done.  ``extra``: device
+        scalars that ride along in the same read-back (the line search's phi'); ``self._extra`` holds them once the record is finished."""
         hyp = self.cfg.hyp
         self.enqueue_times.append(time.time() - train_time)         # everything of the step is queued
         pre2 = self._pre_sqnorm if getattr(self, "_pre_sqnorm", None) is not None else torch.zeros(1, device=norms2.device)
@@ -938,7 +1124,7 @@ class FullBatchTrainer:
             clipped = self.engine.clipped_all.sum().reshape(1)
             if self.multi:
                 torch.distributed.all_reduce(clipped)
-        dev = torch.cat([loss_k, correct_k, sq_k, norms2, pre2, clipped])
+        dev = torch.cat([loss_k, correct_k, sq_k, norms2, pre2, clipped] + ([] if extra is None else [extra]))
         host = self._pinned.pop() if self._pinned and self._pinned[-1].numel() == dev.numel() else torch.empty(dev.numel(), dtype=torch.float32, pin_memory=True)
         host.copy_(dev, non_blocking=True)
         done = torch.cuda.Event(enable_timing=True)
@@ -966,6 +1152,7 @@ class FullBatchTrainer:
         K = self.n_chunks
         loss_k, correct_k, sq_k, (gn2, pn2), pre2, clipped = (host[:K], host[K:2 * K], host[2 * K:3 * K], host[3 * K:3 * K + 2], host[3 * K + 2],
                                                               host[3 * K + 3])
+        self._extra = host[3 * K + 4:].tolist()
         for idx, entry in enumerate(sq_k.sqrt().tolist()):
             stats.raw(f"grad_norm_train_{idx}").append(entry)
         # sequential fp32 sum, like the reference's `step_loss += chunk_loss` (np.cumsum accumulates strictly left to right)

@@ -52,7 +52,7 @@ int32_t fb_entry_kind(int32_t i);
  * for another `which`) and, for 0 <= i < that number, field i in declaration order: its name, byte offset, byte size and type code (as above). */
 int32_t fb_struct_field(int32_t which, int32_t i, const char** name, int32_t* offset, int32_t* size, char* code);
 int32_t fb_struct_size(int32_t which);           /* sizeof, -1 for an unknown struct */
-/* value of a constant of this header by name: "FB_MT_BLOCKS", "FB_PROF_CLASSES", "FB_PROF_INFO"; -1 for any other name */
+/* value of a constant of this header by name: "FB_MT_BLOCKS", "FB_PROF_CLASSES", "FB_PROF_INFO", "FB_WOLFE_VEC", "FB_WOLFE_BLOCK"; -1 for any other name */
 int32_t fb_abi_constant(const char* name);
 
 /* Optional measurement aid (the only process-global state in the library, off by default): while enabled every
@@ -399,6 +399,23 @@ int fb_mt_agc_sgd(float* theta, float* grad, float* mom, int64_t n, const float*
  * not finite, ak or one_plus_ak not finite. */
 int fb_mt_fista(float* theta, float* grad, float* x_minus, int64_t n, const float* gnorm2, float grad_clip, int32_t torch_clip, float lr, float ak,
                 float one_plus_ak, void* stream);
+/* Strong-Wolfe line search (hyp.optim.line_search=wolfe: the reference's WolfeGradientDescent; additive, ABI v17): the arithmetic of one search
+ * on [0, n) of the pointers given.  Every product-and-sum is one fused multiply-add (torch's add(other, alpha=) on a CPU with FMA units, and the
+ * instructions of fb_mt_clip_sgd).  All pointers 16-byte aligned, any n.  The reductions write per-workgroup partials to ws (FB_MT_BLOCKS floats)
+ * and finish them in double in a fixed order that depends on n alone: no atomics, the same bits on every launch.
+ *   fb_mt_wolfe_direction: d = fma(wd, theta, grad);  mom = first ? d : fma(1 - dampening, d, momentum mom)  (momentum != 0: the bits
+ *       fb_mt_clip_sgd writes without a clip; momentum == 0: mom is not touched and may be NULL);  p = -(nesterov ? fma(momentum, mom, d) : mom),
+ *       -d for momentum == 0;  theta0 = theta;  out[0] = sum d p.
+ *   fb_mt_wolfe_trial:     theta = fma(step, p, theta0)   (step = float(lr alpha), formed by the host in double).
+ *   fb_mt_wolfe_phi_grad:  out[0] = sum fma(wd, theta, grad) p; writes nothing else but ws.
+ * A launch covers FB_WOLFE_VEC floats per lane, FB_WOLFE_BLOCK lanes per workgroup, at most FB_MT_BLOCKS workgroups per pass of its stride loop.
+ * Refused without a launch: null pointers, n < 0, a misaligned pointer, a scalar that is not finite. */
+#define FB_WOLFE_VEC 4
+#define FB_WOLFE_BLOCK 256
+int fb_mt_wolfe_direction(const float* theta, const float* grad, float* mom, float* p, float* theta0, int64_t n, float weight_decay, float momentum,
+                          float dampening, int32_t nesterov, int32_t first_step, float* out, float* ws, void* stream);
+int fb_mt_wolfe_trial(float* theta, const float* theta0, const float* p, int64_t n, float step, void* stream);
+int fb_mt_wolfe_phi_grad(const float* theta, const float* grad, const float* p, int64_t n, float weight_decay, float* out, float* ws, void* stream);
 
 #ifdef __cplusplus
 }
