@@ -238,6 +238,140 @@ def within_bound(got, ref, bound):
     return float(ratio[i]), i
 
 
+# ----------------------------------------------------------------------------------------------------------------------------------
+# Elementwise bounds of the bf16 kernels that do the work (convolutions on the matrix pipe, BatchNorm apply / backward apply, pools): the
+# float64 reference of the same operation on the same bf16 operands, and a bound per ELEMENT that follows from the arithmetic -- fp32
+# accumulation of exact products, then ONE rounding to bf16 (to nearest even).  Shared by tests/test_cpu_ops_bounds.py (torch emulations +
+# planted errors: the checker is shown to bite) and tests/test_gpu_ops_bounds.py (the kernels).
+U_ACC = 2.0 ** -23       # one accumulation step of the matrix pipe: a WHOLE fp32 ulp, see mfma_sum_bound
+
+
+def half_ulp_bf16(v):
+    """Half a bf16 ulp in the binade of v >= 0: 2^(floor(log2(max(v, 2^-126))) - 8), float64, elementwise.  bf16 keeps 8 significand bits (one
+    implicit + seven stored): the spacing of its values in [2^e, 2^(e+1)) is 2^(e-7), and round-to-nearest lands within half of that, 2^(e-8) --
+    a unit roundoff of 2^-8.  Relative to the value itself half an ulp ranges from 2^-8 at the bottom of a binade down to 2^-9 at its top: the
+    2^-9 quoted loosely elsewhere is that MINIMUM, not a bound (an honest fp32-accumulate, round-to-nearest-even emulation exceeds a 2^-9
+    bound by 1.6 - 2.0 x).  floor(log2) is taken exactly, from the
+    float64 exponent (frexp), not from a rounded logarithm.  Below the normal range (2^-126) the spacing stays that of the lowest binade."""
+    v = torch.as_tensor(v, dtype=torch.float64).clamp_min(2.0 ** -126)
+    _, e = torch.frexp(v)                                  # v = m 2^e with m in [0.5, 1): floor(log2 v) = e - 1
+    return torch.exp2((e - 9).double())
+
+
+def mfma_sum_bound(A, K):
+    """|fp32 sum of K exact products - their exact sum| <= (K + 1) U_ACC A, with A the sum of the products' absolute values (the same float64
+    convolution applied to |x| and |w|).  A product of two bf16 values has 16 significand bits: exact in fp32.  Every accumulation step adds
+    to a partial sum of magnitude <= A (1 + small) and loses at most one fp32 ulp of it, U_ACC = 2^-23 relative -- a whole ulp, not half:
+    fullbatchtraining_amd/csrc/common.h records at mma_split6 (measured by tools/mfma_accum_probe.hip) that the matrix pipe TRUNCATES small addends against a large
+    accumulator.  K products take at most K additions however they are ordered, blocked into 32-deep instructions or split across waves
+    (a tree over K leaves has K - 1 inner nodes; one more for a zero-started accumulator); + 1 absorbs the second-order terms.  So the bound
+    holds for every tile shape and K-split and carries no constant fitted to a kernel.  What it can see: with K <= 576 it stays below half a
+    bf16 ulp of a typical output, and one-ulp errors (truncation, a second rounding, a value off by one ulp) exceed the total; at K >= 2048
+    the accumulation term dominates the rounding term and such errors are no longer seen -- errors of the size of one missing product
+    (a dropped tap, a wrong row, exchanged channels) still are, at every K."""
+    return (int(K) + 1) * U_ACC * A
+
+
+def rounded_to_bf16_bound(ref, E):
+    """Bound on |stored - ref| for a value stored with ONE round-to-nearest-even to bf16 when E bounds |fp32 value before rounding - ref|:
+    half_ulp_bf16(|ref| + E) + E.  The fp32 value lies within E of ref, so its magnitude is at most |ref| + E and the rounding moves it by at
+    most half an ulp of that magnitude's binade; a value that rounds UP into the next binade (to the power of two itself) moved by at most
+    half an ulp of the binade it came from."""
+    ref = torch.as_tensor(ref, dtype=torch.float64)
+    E = torch.as_tensor(E, dtype=torch.float64, device=ref.device)
+    return half_ulp_bf16(ref.abs() + E) + E
+
+
+def block_stat_bounds(r, E, block=128):
+    """Per-(block, channel) sums and sums of squares of the fp32 accumulators of a convolution (fb_conv2d's stat_partial) against float64.
+    ``r`` [M, C] float64 reference in pixel order, ``E`` [M, C] the bound on each accumulator (mfma_sum_bound); the last block is partly
+    filled when M % block != 0.  -> (sum, bound_sum, sumsq, bound_sumsq), each [ceil(M / block), C].  Each accumulator a_p is within E_p of
+    r_p: that alone moves the sum by sum E_p and the sum of squares by sum (2 |r_p| E_p + E_p^2).  Adding ``block`` fp32 values of
+    magnitude <= |r_p| + E_p in any order takes block - 1 additions, each within 2^-24 of a partial sum that is at most sum (|r_p| + E_p):
+    block 2^-24 sum (|r_p| + E_p); the squares carry one rounding more (the product, or none where it is fused): block + 1."""
+    M, C = r.shape
+    nblk = -(-M // block)
+    pad = nblk * block - M
+
+    def blocks(t):
+        if pad:
+            t = torch.cat([t, torch.zeros(pad, C, dtype=t.dtype, device=t.device)])
+        return t.view(nblk, block, C).sum(1)
+
+    mag = r.abs() + E
+    s, q = blocks(r), blocks(r * r)
+    bs = blocks(E) + block * U32 * blocks(mag)
+    bq = blocks(2 * r.abs() * E + E * E) + (block + 1) * U32 * blocks(mag * mag)
+    return s, bs, q, bq
+
+
+def bn_apply_ref(x, scale, shift, res=None, rscale=None, rshift=None):
+    """fb_bn_apply before ReLU and rounding, float64: v = x scale + shift (+ res | + res rscale + rshift), all operands already broadcast to
+    x's shape -> (v, e) with e = 5 * 2^-24 (|x scale| + |shift| + |res rscale| + |rshift|): at most five fp32 roundings on the path (two
+    products, three sums; fewer where the compiler fuses), each relative to a partial result no larger than the sum of the terms'
+    magnitudes."""
+    x = x.double()
+    v = x * scale.double() + shift.double()
+    mag = (x * scale.double()).abs() + shift.double().abs()
+    if res is not None:
+        t = res.double() * rscale.double() if rscale is not None else res.double()
+        v = v + t
+        mag = mag + t.abs()
+        if rshift is not None:
+            v = v + rshift.double()
+            mag = mag + rshift.double().abs()
+    return v, 5 * U32 * mag
+
+
+def bn_mask_check(bits, v, e, out=None, relu=False):
+    """The ReLU mask bit of fb_bn_apply (1 = the fp32 value is > 0) against the float64 value ``v`` with its bound ``e``: the bit must equal
+    v > 0 wherever |v| > e; inside that band the fp32 value may have either sign and either bit is accepted.  Where the bit is set and ReLU
+    is on, the stored output must not be negative.  -> (number of wrong bits outside the band, share of elements inside the band, number
+    of negative outputs under a set bit)."""
+    bits = bits.bool()
+    band = v.abs() <= e
+    wrong = (bits != (v > 0)) & ~band
+    neg = int((bits & (out.double() < 0)).sum()) if (relu and out is not None) else 0
+    return int(wrong.sum()), float(band.double().mean()), neg
+
+
+def padding_exact_zero(t, real):
+    """True if every element of the padding images of ``t`` ([n, ...], ``real`` [n] bool: the images that are not padding) is EXACTLY zero --
+    all bits clear, so a -0 or a denormal fails: fb_bn_apply writes the padding pixels of a ragged statistics group, their mask bytes and
+    their pooled output as zero bits.  Works on bf16 / fp32 values, mask bytes and booleans."""
+    pad = t[~real].contiguous()
+    if pad.numel() == 0:
+        return True
+    if pad.dtype == torch.bool:
+        return not bool(pad.any())
+    if pad.is_floating_point():
+        pad = pad.view({2: torch.int16, 4: torch.int32, 8: torch.int64}[pad.element_size()])
+    return int((pad != 0).sum()) == 0
+
+
+def bn_dx_ref(coef_dy, coef_x, coef_0, dy, x):
+    """fb_bn_dx (fullbatchtraining_amd/csrc/common.h): dx = fma(c_dy, dy, fma(c_x, x, c_0)) -> (reference, E) with E = 2 * 2^-24 (|c_dy dy| + |c_x x| + |c_0|): two
+    fused multiply-adds, one rounding each, of partial results no larger than the sum of the three terms' magnitudes."""
+    a, b, c = coef_dy.double() * dy.double(), coef_x.double() * x.double(), coef_0.double()
+    return a + b + c, 2 * U32 * (a.abs() + b.abs() + c.abs())
+
+
+def bn_case(C, hw, ipg, groups, valid, seed=4):
+    """Inputs of the BatchNorm bound tests for the shape (channels, map size, images per group, groups, real images per group), NCHW fp32
+    tensors holding bf16-exact values: x (padding images [valid, ipg) of every group exact zeros, as the engine stores them), res, dout,
+    and per-group gamma, beta, rscale, rshift [groups, C] (fp32)."""
+    gen = torch.Generator().manual_seed(seed + C + hw)
+    n = ipg * groups
+    x = (torch.randn(n, C, hw, hw, generator=gen) * 1.5 + 0.3).bfloat16().float()
+    res = torch.randn(n, C, hw, hw, generator=gen).bfloat16().float()
+    dout = torch.randn(n, C, hw, hw, generator=gen).bfloat16().float()
+    gamma, beta = torch.rand(groups, C, generator=gen) + 0.5, torch.randn(groups, C, generator=gen) * 0.1
+    rscale, rshift = torch.rand(groups, C, generator=gen) + 0.5, torch.randn(groups, C, generator=gen) * 0.3
+    real = (torch.arange(n) % ipg) < valid
+    x[~real] = 0
+    return dict(x=x, res=res, dout=dout, gamma=gamma, beta=beta, rscale=rscale, rshift=rshift, real=real)
+
+
 def running_mean_ref(a0, rows, counter0):
     """The running mean a_{j+1} = a_j + (v_j - a_j) / (c + j + 1) of fb_mt_accumulate (and of the mean inside fb_mt_fd_combine_accumulate) as a
     float64 recurrence, with the bound B carried alongside: B += u * (3 |v_j - a_j| / (c+j+1) + |a_{j+1}|) per folded chunk (the subtraction, the

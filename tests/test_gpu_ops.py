@@ -46,22 +46,25 @@ def krsc(w):  # [co, ci, kh, kw] -> [co, kh*kw, ci]
     return w.permute(0, 2, 3, 1).reshape(w.shape[0], -1, w.shape[1]).contiguous()
 
 
+CONV_FWD_CASES = [(64, 64, 3, 1, 8, 8), (64, 128, 3, 2, 8, 8), (128, 256, 1, 1, 4, 16),
+                  (32, 64, 1, 1, 8, 4), (256, 256, 3, 1, 4, 32), (96, 64, 3, 1, 6, 3),
+                  (64, 64, 3, 1, 32, 2), (128, 128, 3, 1, 16, 3), (64, 128, 3, 1, 16, 2),   # LDS-halo kernel
+                  (256, 128, 3, 1, 8, 4), (128, 64, 3, 1, 8, 12), (192, 64, 3, 1, 32, 1),
+                  (64, 64, 3, 1, 8, 2400), (64, 128, 3, 1, 16, 300), (64, 64, 3, 1, 32, 160),   # > 2 tiles per persistent workgroup
+                  (32, 64, 1, 1, 32, 40), (32, 64, 1, 1, 32, 300),   # stem on patches: streaming K = 32 kernel (bf16), grid-stride
+                  (64, 128, 3, 2, 32, 3), (128, 256, 3, 2, 16, 6), (96, 64, 3, 2, 16, 4),   # more stride-2 shapes
+                  (128, 128, 3, 1, 4, 48), (512, 512, 3, 1, 4, 272), (64, 256, 3, 1, 4, 16), (64, 64, 3, 1, 4, 32),   # 4x4 maps: compact halo layout (bf16)
+                  # short-K 1x1 convolutions: streaming kernel (bf16), every (K, channels-per-wave) variant, ragged pixel counts,
+                  # several units per persistent workgroup
+                  (64, 128, 1, 1, 16, 3), (128, 256, 1, 1, 8, 5), (256, 512, 1, 1, 4, 16), (256, 1024, 1, 1, 14, 2), (64, 256, 1, 1, 8, 3),
+                  (128, 128, 1, 1, 8, 40), (256, 128, 1, 1, 6, 3), (64, 128, 1, 1, 6, 3), (64, 128, 1, 1, 16, 700), (256, 256, 1, 1, 14, 300),
+                  # 1x1 with K >= 512: persistent GEMM tiles through a three-stage LDS ring (bf16); ragged pixel counts, one and several
+                  # tiles per workgroup, one to sixteen channel tiles
+                  (512, 128, 1, 1, 8, 5), (1024, 256, 1, 1, 14, 3), (2048, 512, 1, 1, 7, 4), (512, 2048, 1, 1, 7, 2), (576, 128, 1, 1, 14, 400)]
+
+
 @pytest.mark.parametrize("dtype", DTYPES)
-@pytest.mark.parametrize("cin,cout,k,stride,hw,n", [(64, 64, 3, 1, 8, 8), (64, 128, 3, 2, 8, 8), (128, 256, 1, 1, 4, 16),
-                                                   (32, 64, 1, 1, 8, 4), (256, 256, 3, 1, 4, 32), (96, 64, 3, 1, 6, 3),
-                                                   (64, 64, 3, 1, 32, 2), (128, 128, 3, 1, 16, 3), (64, 128, 3, 1, 16, 2),   # LDS-halo kernel
-                                                   (256, 128, 3, 1, 8, 4), (128, 64, 3, 1, 8, 12), (192, 64, 3, 1, 32, 1),
-                                                   (64, 64, 3, 1, 8, 2400), (64, 128, 3, 1, 16, 300), (64, 64, 3, 1, 32, 160),   # > 2 tiles per persistent workgroup
-                                                   (32, 64, 1, 1, 32, 40), (32, 64, 1, 1, 32, 300),   # stem on patches: streaming K = 32 kernel (bf16), grid-stride
-                                                   (64, 128, 3, 2, 32, 3), (128, 256, 3, 2, 16, 6), (96, 64, 3, 2, 16, 4),   # more stride-2 shapes
-                                                   (128, 128, 3, 1, 4, 48), (512, 512, 3, 1, 4, 272), (64, 256, 3, 1, 4, 16), (64, 64, 3, 1, 4, 32),   # 4x4 maps: compact halo layout (bf16)
-                                                   # short-K 1x1 convolutions: streaming kernel (bf16), every (K, channels-per-wave) variant, ragged pixel counts,
-                                                   # several units per persistent workgroup
-                                                   (64, 128, 1, 1, 16, 3), (128, 256, 1, 1, 8, 5), (256, 512, 1, 1, 4, 16), (256, 1024, 1, 1, 14, 2), (64, 256, 1, 1, 8, 3),
-                                                   (128, 128, 1, 1, 8, 40), (256, 128, 1, 1, 6, 3), (64, 128, 1, 1, 6, 3), (64, 128, 1, 1, 16, 700), (256, 256, 1, 1, 14, 300),
-                                                   # 1x1 with K >= 512: persistent GEMM tiles through a three-stage LDS ring (bf16); ragged pixel counts, one and several
-                                                   # tiles per workgroup, one to sixteen channel tiles
-                                                   (512, 128, 1, 1, 8, 5), (1024, 256, 1, 1, 14, 3), (2048, 512, 1, 1, 7, 4), (512, 2048, 1, 1, 7, 2), (576, 128, 1, 1, 14, 400)])
+@pytest.mark.parametrize("cin,cout,k,stride,hw,n", CONV_FWD_CASES)
 def test_conv_fwd_and_stats(dtype, cin, cout, k, stride, hw, n, monkeypatch):
     lib = _lib()
     torch.manual_seed(0)
@@ -110,22 +113,25 @@ def test_conv_fwd_and_stats(dtype, cin, cout, k, stride, hw, n, monkeypatch):
         assert torch.equal(out, out2) and torch.equal(stat, stat2)
 
 
+CONV_DGRAD_CASES = [(64, 64, 3, 1, 8, 8, 0), (64, 128, 3, 2, 8, 8, 2), (128, 64, 1, 1, 4, 16, 1),
+                    (64, 64, 3, 1, 8, 4, 1), (256, 128, 3, 2, 8, 4, 0),
+                    (64, 64, 3, 1, 32, 2, 1), (128, 64, 3, 1, 16, 2, 0), (64, 64, 3, 1, 16, 2, 2),  # halo kernel
+                    (128, 256, 3, 1, 8, 8, 1), (128, 64, 3, 1, 8, 4, 2), (256, 256, 3, 1, 8, 4, 0),
+                    (64, 64, 3, 1, 32, 136, 1), (128, 64, 3, 1, 16, 600, 0),   # persistent workgroups, several tiles each
+                    # stride-2 quad kernel (bf16): dY 16x16 / 8x8 / 4x4, ragged image counts, all addend modes
+                    (64, 128, 3, 2, 32, 3, 2), (128, 256, 3, 2, 16, 5, 1), (64, 64, 3, 2, 8, 11, 2),
+                    (128, 96, 3, 2, 16, 2, 0), (64, 128, 3, 2, 32, 70, 0),
+                    (256, 128, 3, 1, 4, 32, 1), (128, 256, 3, 1, 4, 16, 0), (512, 512, 3, 1, 4, 272, 1), (64, 64, 3, 1, 4, 16, 2),   # 4x4 maps: compact halo layout
+                    # 1x1 input gradients: streaming kernel (K = the forward layer's output channels <= 256), with / without the
+                    # same-shape addend; pooled addend and K = 512 stay on the implicit GEMM
+                    (256, 128, 1, 1, 8, 5, 0), (1024, 256, 1, 1, 7, 4, 1), (512, 128, 1, 1, 8, 3, 1), (128, 64, 1, 1, 16, 300, 1),
+                    (256, 64, 1, 1, 8, 6, 2), (256, 512, 1, 1, 4, 16, 1),
+                    # 1x1 input gradients with K >= 512 (the GEMM kernel; with an addend they stay on the implicit GEMM)
+                    (128, 512, 1, 1, 8, 5, 0), (256, 1024, 1, 1, 14, 3, 0), (512, 2048, 1, 1, 7, 6, 0), (256, 1024, 1, 1, 14, 3, 1)]
+
+
 @pytest.mark.parametrize("dtype", DTYPES)
-@pytest.mark.parametrize("cin,cout,k,stride,hw,n,amode", [(64, 64, 3, 1, 8, 8, 0), (64, 128, 3, 2, 8, 8, 2), (128, 64, 1, 1, 4, 16, 1),
-                                                          (64, 64, 3, 1, 8, 4, 1), (256, 128, 3, 2, 8, 4, 0),
-                                                          (64, 64, 3, 1, 32, 2, 1), (128, 64, 3, 1, 16, 2, 0), (64, 64, 3, 1, 16, 2, 2),  # halo kernel
-                                                          (128, 256, 3, 1, 8, 8, 1), (128, 64, 3, 1, 8, 4, 2), (256, 256, 3, 1, 8, 4, 0),
-                                                          (64, 64, 3, 1, 32, 136, 1), (128, 64, 3, 1, 16, 600, 0),   # persistent workgroups, several tiles each
-                                                          # stride-2 quad kernel (bf16): dY 16x16 / 8x8 / 4x4, ragged image counts, all addend modes
-                                                          (64, 128, 3, 2, 32, 3, 2), (128, 256, 3, 2, 16, 5, 1), (64, 64, 3, 2, 8, 11, 2),
-                                                          (128, 96, 3, 2, 16, 2, 0), (64, 128, 3, 2, 32, 70, 0),
-                                                          (256, 128, 3, 1, 4, 32, 1), (128, 256, 3, 1, 4, 16, 0), (512, 512, 3, 1, 4, 272, 1), (64, 64, 3, 1, 4, 16, 2),   # 4x4 maps: compact halo layout
-                                                          # 1x1 input gradients: streaming kernel (K = the forward layer's output channels <= 256), with / without the
-                                                          # same-shape addend; pooled addend and K = 512 stay on the implicit GEMM
-                                                          (256, 128, 1, 1, 8, 5, 0), (1024, 256, 1, 1, 7, 4, 1), (512, 128, 1, 1, 8, 3, 1), (128, 64, 1, 1, 16, 300, 1),
-                                                          (256, 64, 1, 1, 8, 6, 2), (256, 512, 1, 1, 4, 16, 1),
-                                                          # 1x1 input gradients with K >= 512 (the GEMM kernel; with an addend they stay on the implicit GEMM)
-                                                          (128, 512, 1, 1, 8, 5, 0), (256, 1024, 1, 1, 14, 3, 0), (512, 2048, 1, 1, 7, 6, 0), (256, 1024, 1, 1, 14, 3, 1)])
+@pytest.mark.parametrize("cin,cout,k,stride,hw,n,amode", CONV_DGRAD_CASES)
 def test_conv_dgrad(dtype, cin, cout, k, stride, hw, n, amode, monkeypatch):
     lib = _lib()
     torch.manual_seed(1)
