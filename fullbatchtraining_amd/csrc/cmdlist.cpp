@@ -105,6 +105,8 @@ constexpr Entry kEntries[] = {
     FB_RECORDABLE(fb_mt_fista),
     // strong-Wolfe line search (hyp.optim.line_search=wolfe)
     FB_RECORDABLE(fb_mt_wolfe_direction), FB_RECORDABLE(fb_mt_wolfe_trial), FB_RECORDABLE(fb_mt_wolfe_phi_grad),
+    // loss-landscape cruncher (cfg.viz)
+    FB_RECORDABLE(fb_mt_landscape_point), FB_HOST(fb_mt_landscape_point_supported),
 };
 constexpr int kNumEntries = sizeof(kEntries) / sizeof(kEntries[0]);
 constexpr bool launches_take_a_stream() {
@@ -172,6 +174,9 @@ extern "C" int32_t fb_abi_constant(const char* name) {
     if (strcmp(name, "FB_PROF_INFO") == 0) return FB_PROF_INFO;
     if (strcmp(name, "FB_WOLFE_VEC") == 0) return FB_WOLFE_VEC;
     if (strcmp(name, "FB_WOLFE_BLOCK") == 0) return FB_WOLFE_BLOCK;
+    if (strcmp(name, "FB_LANDSCAPE_VEC") == 0) return FB_LANDSCAPE_VEC;
+    if (strcmp(name, "FB_LANDSCAPE_BLOCK") == 0) return FB_LANDSCAPE_BLOCK;
+    if (strcmp(name, "FB_LANDSCAPE_BLOCKS") == 0) return FB_LANDSCAPE_BLOCKS;
     return -1;
 }
 

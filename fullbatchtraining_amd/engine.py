@@ -621,20 +621,20 @@ class Engine:
     def prep_weights(self, theta, nsets, per_chunk=False):
         """fp32 master (one shared set or one per chunk) -> compute-dtype forward and transposed dgrad copies."""
         slot = 1 if per_chunk else 0
+        self._replayable(("prep", theta.data_ptr(), nsets, slot), lambda: self._prep_weights_body(theta, nsets, slot))
+
+    def _prep_weights_body(self, theta, nsets, slot, dgrad=True):
+        """The launches of ``prep_weights`` (``dgrad=False``: the forward copies alone, for passes that have no backward)."""
         wf, wd = self.w_fwd[slot], self.w_dgrad[slot]
         es = wf.element_size()
-
-        def body():
-            for li, L in enumerate(self.plan.layers):
-                dst_d = wd.data_ptr() + es * L.wc_off if L is not self.plan.stem else None
-                am = None
-                if self.f32_split == "f16x2":        # one scale per layer and weight set, shared by its forward and transposed copies;
-                    am = self.w_amax[slot][li].data_ptr()                       # the copies are then written as fp16x2 planes
-                    call("fb_absmax", theta.data_ptr() + 4 * L.w_off, L.cout * L.taps * L.cin_real, nsets, self.plan.P, 1, am)
-                call("fb_weight_prep", theta.data_ptr() + 4 * L.w_off, self.plan.P, self.plan.wc_total, nsets, L.cout, L.taps, L.cin_real,
-                     L.cin_pad, wf.data_ptr() + es * L.wc_off, dst_d, self.dtc, am)
-
-        self._replayable(("prep", theta.data_ptr(), nsets, slot), body)
+        for li, L in enumerate(self.plan.layers):
+            dst_d = wd.data_ptr() + es * L.wc_off if (dgrad and L is not self.plan.stem) else None
+            am = None
+            if self.f32_split == "f16x2":        # one scale per layer and weight set, shared by its forward and transposed copies;
+                am = self.w_amax[slot][li].data_ptr()                       # the copies are then written as fp16x2 planes
+                call("fb_absmax", theta.data_ptr() + 4 * L.w_off, L.cout * L.taps * L.cin_real, nsets, self.plan.P, 1, am)
+            call("fb_weight_prep", theta.data_ptr() + 4 * L.w_off, self.plan.P, self.plan.wc_total, nsets, L.cout, L.taps, L.cin_real,
+                 L.cin_pad, wf.data_ptr() + es * L.wc_off, dst_d, self.dtc, am)
 
     def _amax(self, t, numel, G):
         """Device pointer of the per-chunk largest magnitudes (G floats) of the first ``numel`` values of ``t`` (fp16x2 split scales),
@@ -792,9 +792,12 @@ class Engine:
         hw = plan.h_final * plan.h_final
         call("fb_head_pool", a.data_ptr(), self.feat.data_ptr(), n, hw, plan.feat, self.dtc)
         pstride = plan.P if wsets > 1 else 0
+        # (eval mode has no per-chunk statistics: ``_head_groups`` = (groups, images per group, loss, correct) lets one pass of n images report the
+        # means of several blocks, into the caller's arrays -- the landscape pass)
+        hG, himgs, hloss, hcorrect = getattr(self, "_head_groups", None) or (G, self.chunk, self.loss, self.correct)
         call("fb_head_loss", self.feat.data_ptr(), theta.data_ptr() + 4 * plan.fcw_off, theta.data_ptr() + 4 * plan.fcb_off, pstride,
-             labels.data_ptr(), self.logits.data_ptr(), self.dlogits.data_ptr(), self.loss.data_ptr(), self.correct.data_ptr(), G,
-             self.chunk, plan.feat, plan.classes,
+             labels.data_ptr(), self.logits.data_ptr(), self.dlogits.data_ptr(), _ptr(hloss), _ptr(hcorrect), hG,
+             himgs, plan.feat, plan.classes,
              # the training loss of get_loss_fn; evaluation always uses plain cross entropy (reference training.py:345)
              0.0 if getattr(self, "_eval", False) else float(self.label_smoothing), 0 if getattr(self, "_eval", False) else int(self.only_incorrect))
         return a
@@ -1528,6 +1531,87 @@ class Engine:
     def sam_restore(self):
         """SAM second step, first half (sam.py:72-77): theta -= e_w (the same rounding as the reference's ``p.sub_(e_w)``)."""
         call("fb_mt_sam_restore", self.theta.data_ptr(), self.e_w.data_ptr(), self.plan.P)
+
+    # ---- loss landscape (cfg.viz): the grid points theta = base + x dx + y dy, each evaluated in eval mode over staged patches
+    def landscape_fused(self):
+        """Whether a grid point is ONE fb_mt_landscape_point launch (offset + forward weight copies); the fp16x2 weight planes take the
+        composition offset-only launch + fb_weight_prep per layer."""
+        return bool(lib.load().fb_mt_landscape_point_supported(self.dtc, 1 if self.f32_split == "f16x2" else 0))
+
+    def landscape_begin(self, dx, dy):
+        """Snapshot ``self.theta`` as the base point and take the two directions (lists in ``model.parameters()`` layout, or flat arena
+        vectors).  The alignment gaps of the direction arenas are zero: they stay zero at every point."""
+        self.ls_base = self.theta.detach().clone()
+        self.ls_dx = (dx if torch.is_tensor(dx) else self.flatten(dx)).to(self.device, torch.float32).contiguous()
+        self.ls_dy = (dy if torch.is_tensor(dy) else self.flatten(dy)).to(self.device, torch.float32).contiguous()
+        if self.ls_dx.numel() != self.plan.P or self.ls_dy.numel() != self.plan.P:
+            raise lib.EngineError(f"landscape_begin: directions of {self.ls_dx.numel()} / {self.ls_dy.numel()} elements for an arena of {self.plan.P}")
+        self.ls_xy = torch.zeros(2, device=self.device, dtype=torch.float32)
+        self.ls_out, self._ls_host = None, None
+
+    def landscape_end(self):
+        """The arena holds the base point again, bit for bit, and the weight copies are the base point's."""
+        self.theta.copy_(self.ls_base)
+        self.prep_weights(self.theta, 1)
+        self.ls_base = self.ls_dx = self.ls_dy = self.ls_xy = self.ls_out = None
+
+    def landscape_pieces(self, n_images, block):
+        """How ``landscape_point`` cuts ``n_images`` staged images in blocks of ``block`` (the last one may be ragged) into forward passes:
+        [(first image, images, head groups)] -- whole blocks, as many as the activation buffers hold, each reporting its own mean through
+        a head group; a block larger than the buffers in pieces of at most ``G * chunk`` images (head groups 1: the caller weights them)."""
+        cap = self.G * self.chunk
+        out, i = [], 0
+        while i < n_images:
+            if block <= cap:
+                k = min(cap // block, (n_images - i) // block)
+                n, groups = (k * block, k) if k > 0 else (n_images - i, 1)            # (the ragged last block on its own)
+            else:
+                n, groups = min(cap, block - (i % block), n_images - i), 1
+            out.append((i, n, groups))
+            i += n
+        return out
+
+    def landscape_point(self, x, y, patches, labels, block):
+        """Set theta = base + x dx + y dy and evaluate it in eval mode (BatchNorm with the running statistics, plain cross entropy) over the
+        staged ``patches`` / ``labels`` in blocks of ``block`` images, without a host wait: one recorded list -- the point kernel, the
+        BatchNorm coefficients of the new affine parameters, every piece's forward pass and head (which write their means and counts straight
+        into the position's device array), |theta|^2 -- replayed after a two-float device write.  Returns the device tensor
+        [loss of every head group..., correct of every head group..., |theta|^2, |theta|^2], laid out by ``landscape_pieces``; the caller
+        reads it back (the only host wait of the position).  ``landscape_begin`` first; the running statistics are never written."""
+        pieces = self.landscape_pieces(patches.shape[0], block)
+        n_out = sum(g for _, _, g in pieces)
+        if self.ls_out is None or self.ls_out.numel() != 2 * n_out + 2:
+            self.ls_out = torch.zeros(2 * n_out + 2, device=self.device, dtype=torch.float32)
+        if self._ls_host is None:
+            self._ls_host = torch.zeros(2, dtype=torch.float32).pin_memory()
+        self._ls_host[0], self._ls_host[1] = float(x), float(y)      # (pinned: the caller's read-back of this point precedes the next write)
+        self.ls_xy.copy_(self._ls_host, non_blocking=True)
+        out, fused = self.ls_out, self.landscape_fused()
+
+        def body():
+            tab = self.sgd_layer_table() if fused else None
+            call("fb_mt_landscape_point", self.theta.data_ptr(), self.ls_base.data_ptr(), self.ls_dx.data_ptr(), self.ls_dy.data_ptr(), self.plan.P,
+                 self.ls_xy.data_ptr(), _ptr(tab), tab.shape[0] if fused else 0, self.w_fwd[0].data_ptr() if fused else None, self.dtc)
+            if not fused:
+                self._prep_weights_body(self.theta, 1, 0, dgrad=False)
+            for L in self.plan.layers:
+                call("fb_bn_eval_coeffs", self.theta.data_ptr() + 4 * L.g_off, self.theta.data_ptr() + 4 * L.b_off,
+                     self.running_mean.data_ptr() + 4 * L.ch_off, self.running_var.data_ptr() + 4 * L.ch_off, BN_EPS, L.scale.data_ptr(),
+                     L.shift.data_ptr(), L.cout)
+            saved, slot = (self.chunk, self.valid), 0
+            try:
+                for i0, n, groups in pieces:
+                    self.chunk, self.valid, self._eval = n, n, True
+                    self._head_groups = (groups, n // groups, out.data_ptr() + 4 * slot, out.data_ptr() + 4 * (n_out + slot))
+                    self.forward(patches[i0:i0 + n], labels[i0:i0 + n], 1, 1, self.theta, 0)
+                    slot += groups
+            finally:
+                (self.chunk, self.valid), self._eval, self._head_groups = saved, False, None
+            call("fb_mt_norms2", self.theta.data_ptr(), self.theta.data_ptr(), self.plan.P, out.data_ptr() + 8 * n_out, self.mt_ws.data_ptr())
+
+        self._replayable(("landscape", patches.data_ptr(), labels.data_ptr(), patches.shape[0], block, out.data_ptr(), self.theta.data_ptr(), self.ls_base.data_ptr(),
+                          self.ls_dx.data_ptr(), self.ls_dy.data_ptr(), self.ls_xy.data_ptr(), self.running_mean.data_ptr(), fused), body)
+        return out
 
     # ------------------------------------------------------------------------------------------------------ evaluation --
     def evaluate_batch(self, patches, labels):

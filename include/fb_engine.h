@@ -52,7 +52,8 @@ int32_t fb_entry_kind(int32_t i);
  * for another `which`) and, for 0 <= i < that number, field i in declaration order: its name, byte offset, byte size and type code (as above). */
 int32_t fb_struct_field(int32_t which, int32_t i, const char** name, int32_t* offset, int32_t* size, char* code);
 int32_t fb_struct_size(int32_t which);           /* sizeof, -1 for an unknown struct */
-/* value of a constant of this header by name: "FB_MT_BLOCKS", "FB_PROF_CLASSES", "FB_PROF_INFO", "FB_WOLFE_VEC", "FB_WOLFE_BLOCK"; -1 for any other name */
+/* value of a constant of this header by name: "FB_MT_BLOCKS", "FB_PROF_CLASSES", "FB_PROF_INFO", "FB_WOLFE_VEC", "FB_WOLFE_BLOCK",
+ * "FB_LANDSCAPE_VEC", "FB_LANDSCAPE_BLOCK", "FB_LANDSCAPE_BLOCKS"; -1 for any other name */
 int32_t fb_abi_constant(const char* name);
 
 /* Optional measurement aid (the only process-global state in the library, off by default): while enabled every
@@ -416,6 +417,26 @@ int fb_mt_wolfe_direction(const float* theta, const float* grad, float* mom, flo
                           float dampening, int32_t nesterov, int32_t first_step, float* out, float* ws, void* stream);
 int fb_mt_wolfe_trial(float* theta, const float* theta0, const float* p, int64_t n, float step, void* stream);
 int fb_mt_wolfe_phi_grad(const float* theta, const float* grad, const float* p, int64_t n, float weight_decay, float* out, float* ws, void* stream);
+/* Loss-landscape cruncher (cfg.viz: the reference's crunch.py, _set_parameter_offset; additive, ABI v17): one grid point in one launch,
+ *   theta = base + (dx x + dy y)       four operations, each rounded on its own as the reference's tensor operations: dx x, dy y, their sum, base + sum
+ * on [0, n) of the pointers given, with (x, y) = xy[0], xy[1] read from DEVICE memory -- a recorded command list is replayed for every point after
+ * a two-float device write -- AND the forward compute-dtype copy [co][tap][ci_pad] of theta for every convolution layer of layer_tab into w_fwd,
+ * written from the same registers (the arena is KRSC: a cast and the padding stride, no transposition).  layer_tab: the DEVICE table of
+ * fb_mt_sgd_prep, [n_layers][8] rows {w_off, Cout, taps, Cin_real, Cin_pad, wc_off, has_dgrad (ignored), 0} sorted by w_off; elements outside
+ * every layer get the offset only; padding columns Cin_real <= ci < Cin_pad are neither read nor written.  layer_tab = NULL (or n_layers = 0):
+ * the offset only -- what a host composes with fb_weight_prep where fb_mt_landscape_point_supported(dtype, f16x2_planes) is 0 (fp16x2 planes).
+ * dtype FB_F32 / FB_BF16.  (0, 0) returns base bit for bit (for finite directions).  theta must not overlap the inputs.  Any 4-byte aligned arena
+ * pointers and any n; 16-byte accesses where the four arena operands share their misalignment; w_fwd 16-byte aligned.  One owner per element, no
+ * atomics: the result does not depend on the grid.  The host checks the table once per (address, n_layers, n) -- one blocking read-back on first
+ * sight.  Refused without a launch: null pointers, n < 0, more than 512 layers, a table without w_fwd, a table that is not sorted, overlaps,
+ * leaves [0, n) or has Cin_real > Cin_pad, an unknown dtype, a misaligned pointer.
+ * A launch covers FB_LANDSCAPE_VEC floats per lane, FB_LANDSCAPE_BLOCK lanes per workgroup, at most FB_LANDSCAPE_BLOCKS workgroups per pass of its stride loop. */
+#define FB_LANDSCAPE_VEC 8
+#define FB_LANDSCAPE_BLOCK 256
+#define FB_LANDSCAPE_BLOCKS 2048
+int fb_mt_landscape_point(float* theta, const float* base, const float* dx, const float* dy, int64_t n, const float* xy,
+                          const int32_t* layer_tab, int32_t n_layers, void* w_fwd, int32_t dtype, void* stream);
+int32_t fb_mt_landscape_point_supported(int32_t dtype, int32_t f16x2_planes);
 
 #ifdef __cplusplus
 }
