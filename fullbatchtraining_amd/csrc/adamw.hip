@@ -10,8 +10,8 @@
 // step_size = lr / (1 - beta1^t) and bc2_sqrt = sqrt(1 - beta2^t) come from the host (formed in double from the step count t).  step_size == 0
 // (lr 0: step 0 of a warm-up) leaves p' = p1 = p bit for bit while m, v advance.  g = m = v = p = 0 (alignment padding of the arena) stays 0.
 // HBM-bound: 16 B read and 12 B written per element without a clip.  One owner per element, no atomics: the result does not depend on the grid.
-// 16-byte loads / stores on the body that is aligned in all four operands, scalar head and tail: any offset into the arena and any n work.
-#include "common.h"
+// 16-byte loads / stores on the body that is aligned in all four operands, scalar head and tail (arena_pass): any offset into the arena and any n work.
+#include "arena_update.h"
 
 namespace {
 
@@ -32,37 +32,11 @@ __global__ __launch_bounds__(256) void mt_adamw_kernel(float* __restrict__ theta
                                                        const float* __restrict__ gnorm2, float grad_clip, int torch_clip, float lr, float wd,
                                                        float b1, float b2, float eps, float step_size, float bc2s) {
     AdamHyp h;
-    h.coef = 1.f;
-    if (grad_clip >= 0.f) {
-        const float norm = sqrtf(gnorm2[0]);
-        const float c = grad_clip / (norm + 1e-6f);
-        if (torch_clip) h.coef = c < 1.f ? c : 1.f;            // clip_grad_norm_: min(1, clip / (norm + 1e-6))
-        else if (norm > grad_clip) h.coef = c;                 // _modify_gradient_params: if norm > clip
-    }
-    const bool write_grad = !torch_clip && h.coef != 1.f;      // (the full-batch closure clips p.grad in place; clip_grad_norm_'s consumer reads only)
+    h.coef = fb_clip_coef(gnorm2, grad_clip, torch_clip);
     h.decay = __fmaf_rn(-lr, wd, 1.f);
     h.b1 = b1; h.omb1 = 1.f - b1; h.b2 = b2; h.omb2 = 1.f - b2; h.eps = eps; h.step_size = step_size; h.bc2s = bc2s;
-    const long long gtid = (long long)blockIdx.x * 256 + threadIdx.x, gsize = (long long)gridDim.x * 256;
-    // ---- the body: elements [head, head + 4 n4), 16-byte aligned in every operand
-    float4* t4 = (float4*)(theta + head); float4* g4 = (float4*)(grad + head);
-    float4* m4 = (float4*)(exp_avg + head); float4* v4 = (float4*)(exp_avg_sq + head);
-    for (long long i = gtid; i < n4; i += gsize) {
-        const float4 p = t4[i], g = g4[i], m = m4[i], v = v4[i];
-        float4 po, go, mo, vo;
-        adamw_update(h, p.x, g.x, m.x, v.x, po.x, go.x, mo.x, vo.x); adamw_update(h, p.y, g.y, m.y, v.y, po.y, go.y, mo.y, vo.y);
-        adamw_update(h, p.z, g.z, m.z, v.z, po.z, go.z, mo.z, vo.z); adamw_update(h, p.w, g.w, m.w, v.w, po.w, go.w, mo.w, vo.w);
-        t4[i] = po; m4[i] = mo; v4[i] = vo;
-        if (write_grad) g4[i] = go;
-    }
-    // ---- the edges: [0, head) and [head + 4 n4, n), one element per thread
-    const long long tail0 = head + 4 * n4, edges = head + (n - tail0);
-    for (long long e = gtid; e < edges; e += gsize) {
-        const long long i = e < head ? e : tail0 + (e - head);
-        float po, go, mo, vo;
-        adamw_update(h, theta[i], grad[i], exp_avg[i], exp_avg_sq[i], po, go, mo, vo);
-        theta[i] = po; exp_avg[i] = mo; exp_avg_sq[i] = vo;
-        if (write_grad) grad[i] = go;
-    }
+    float* const op[4] = {theta, grad, exp_avg, exp_avg_sq};
+    arena_pass(op, n, head, n4, !torch_clip && h.coef != 1.f, [&h](float (&x)[4]) { adamw_update(h, x[0], x[1], x[2], x[3], x[0], x[1], x[2], x[3]); });
 }
 
 }  // namespace
@@ -78,16 +52,9 @@ extern "C" int fb_mt_adamw(float* theta, float* grad, float* exp_avg, float* exp
     if (!(bc2_sqrt > 0.f)) FB_FAIL(FB_ERR_ARG, "fb_mt_adamw: bc2_sqrt=%g must be positive (sqrt(1 - beta2^t), t >= 1)", (double)bc2_sqrt);
     if (((uintptr_t)theta | (uintptr_t)grad | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 3) FB_FAIL(FB_ERR_ARG, "fb_mt_adamw: 4-byte alignment required");
     if (n == 0) return FB_OK;
-    // the vector body needs one misalignment shared by the four operands (ranges of the arenas at one offset have it); otherwise all scalar
-    const unsigned mis = (unsigned)((uintptr_t)theta & 15);
-    const bool same = ((uintptr_t)grad & 15) == mis && ((uintptr_t)exp_avg & 15) == mis && ((uintptr_t)exp_avg_sq & 15) == mis;
-    long long head = same ? ((16 - mis) & 15) / 4 : (long long)n;
-    if (head > n) head = n;
-    const long long n4 = (n - head) / 4;
-    const long long work = n4 > 0 ? n4 : n, want = (work + 255) / 256;
-    const unsigned nb = (unsigned)(want < 1 ? 1 : (want > 2048 ? 2048 : want));
-    hipLaunchKernelGGL(mt_adamw_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, theta, grad, exp_avg, exp_avg_sq, (long long)n, head, n4, gnorm2,
-                       grad_clip, (int)torch_clip, lr, weight_decay, beta1, beta2, eps, step_size, bc2_sqrt);
+    const ArenaSplit s = arena_split({theta, grad, exp_avg, exp_avg_sq}, n);
+    hipLaunchKernelGGL(mt_adamw_kernel, dim3(s.blocks), dim3(256), 0, (hipStream_t)stream, theta, grad, exp_avg, exp_avg_sq, (long long)n, s.head, s.n4,
+                       gnorm2, grad_clip, (int)torch_clip, lr, weight_decay, beta1, beta2, eps, step_size, bc2_sqrt);
     FB_CHECK_LAUNCH("fb_mt_adamw");
     return FB_OK;
 }

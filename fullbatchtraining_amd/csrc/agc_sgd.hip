@@ -38,7 +38,7 @@
 #include <tuple>
 #include <vector>
 
-#include "common.h"
+#include "arena_update.h"
 
 #pragma clang fp contract(off)     // (__fmul_rn / __fadd_rn are plain operators to hipcc: nothing below may be fused beyond the fmas written out)
 
@@ -224,13 +224,7 @@ __global__ __launch_bounds__(AGC_THREADS) void mt_agc_sgd_kernel(const AgcArgs a
     const long long total = pre[R];
 
     AgcHyp h;
-    h.coef = 1.f;
-    if (a.grad_clip >= 0.f) {
-        const float norm = sqrtf(a.gnorm2[0]);
-        const float c = a.grad_clip / (norm + 1e-6f);
-        if (a.torch_clip) h.coef = c < 1.f ? c : 1.f;          // clip_grad_norm_: min(1, clip / (norm + 1e-6))
-        else if (norm > a.grad_clip) h.coef = c;               // _modify_gradient_params: if norm > clip
-    }
+    h.coef = fb_clip_coef(a.gnorm2, a.grad_clip, a.torch_clip);
     h.write_grad = !a.torch_clip && h.coef != 1.f;             // (the full-batch closure clips p.grad in place; the AGC-clipped gradient is never written)
     h.lr = a.lr; h.wd = a.wd; h.mu = a.mu; h.one_minus_damp = 1.f - a.damp; h.clipping = a.clipping; h.eps = a.eps;
     h.nesterov = a.nesterov; h.first = a.first; h.use_mom = a.mu != 0.f; h.read_mom = h.use_mom && !a.first;

@@ -10,8 +10,8 @@
 // xp * 1 - x_minus * 0 = xp as long as x_minus is finite (the engine clones theta into it).  theta = g = x_minus = 0 (alignment padding of the
 // arena) stays 0.  HBM-bound: 12 B read and 8 B written per element without a clip, as fb_mt_clip_sgd with momentum.  One owner per element, no
 // atomics: the result does not depend on the grid.  16-byte loads / stores on the body that is aligned in all three operands, scalar head and
-// tail: any offset into the arena and any n work.
-#include "common.h"
+// tail (arena_pass): any offset into the arena and any n work.
+#include "arena_update.h"
 
 namespace {
 
@@ -36,35 +36,10 @@ __global__ __launch_bounds__(256) void mt_fista_kernel(float* __restrict__ theta
                                                        long long head, long long n4, const float* __restrict__ gnorm2, float grad_clip,
                                                        int torch_clip, float lr, float ak, float one_plus_ak) {
     FistaHyp h;
-    h.coef = 1.f;
-    if (grad_clip >= 0.f) {
-        const float norm = sqrtf(gnorm2[0]);
-        const float c = grad_clip / (norm + 1e-6f);
-        if (torch_clip) h.coef = c < 1.f ? c : 1.f;            // clip_grad_norm_: min(1, clip / (norm + 1e-6))
-        else if (norm > grad_clip) h.coef = c;                 // _modify_gradient_params: if norm > clip
-    }
-    const bool write_grad = !torch_clip && h.coef != 1.f;      // (the full-batch closure clips p.grad in place; clip_grad_norm_'s consumer reads only)
+    h.coef = fb_clip_coef(gnorm2, grad_clip, torch_clip);
     h.lr = lr; h.ak = ak; h.opak = one_plus_ak;
-    const long long gtid = (long long)blockIdx.x * 256 + threadIdx.x, gsize = (long long)gridDim.x * 256;
-    // ---- the body: elements [head, head + 4 n4), 16-byte aligned in every operand
-    float4* t4 = (float4*)(theta + head); float4* g4 = (float4*)(grad + head); float4* x4 = (float4*)(x_minus + head);
-    for (long long i = gtid; i < n4; i += gsize) {
-        const float4 p = t4[i], g = g4[i], x = x4[i];
-        float4 po, go, xo;
-        fista_update(h, p.x, g.x, x.x, po.x, go.x, xo.x); fista_update(h, p.y, g.y, x.y, po.y, go.y, xo.y);
-        fista_update(h, p.z, g.z, x.z, po.z, go.z, xo.z); fista_update(h, p.w, g.w, x.w, po.w, go.w, xo.w);
-        t4[i] = po; x4[i] = xo;
-        if (write_grad) g4[i] = go;
-    }
-    // ---- the edges: [0, head) and [head + 4 n4, n), one element per thread
-    const long long tail0 = head + 4 * n4, edges = head + (n - tail0);
-    for (long long e = gtid; e < edges; e += gsize) {
-        const long long i = e < head ? e : tail0 + (e - head);
-        float po, go, xo;
-        fista_update(h, theta[i], grad[i], x_minus[i], po, go, xo);
-        theta[i] = po; x_minus[i] = xo;
-        if (write_grad) grad[i] = go;
-    }
+    float* const op[3] = {theta, grad, x_minus};
+    arena_pass(op, n, head, n4, !torch_clip && h.coef != 1.f, [&h](float (&x)[3]) { fista_update(h, x[0], x[1], x[2], x[0], x[1], x[2]); });
 }
 
 inline bool finite_f(float x) { return x - x == 0.f; }     // (false for inf and NaN; <cmath>'s isfinite is a device overload here)
@@ -80,16 +55,9 @@ extern "C" int fb_mt_fista(float* theta, float* grad, float* x_minus, int64_t n,
     if (!finite_f(ak) || !finite_f(one_plus_ak)) FB_FAIL(FB_ERR_ARG, "fb_mt_fista: ak=%g / one_plus_ak=%g must be finite", (double)ak, (double)one_plus_ak);
     if (((uintptr_t)theta | (uintptr_t)grad | (uintptr_t)x_minus) & 3) FB_FAIL(FB_ERR_ARG, "fb_mt_fista: 4-byte alignment required");
     if (n == 0) return FB_OK;
-    // the vector body needs one misalignment shared by the three operands (ranges of the arenas at one offset have it); otherwise all scalar
-    const unsigned mis = (unsigned)((uintptr_t)theta & 15);
-    const bool same = ((uintptr_t)grad & 15) == mis && ((uintptr_t)x_minus & 15) == mis;
-    long long head = same ? ((16 - mis) & 15) / 4 : (long long)n;
-    if (head > n) head = n;
-    const long long n4 = (n - head) / 4;
-    const long long work = n4 > 0 ? n4 : n, want = (work + 255) / 256;
-    const unsigned nb = (unsigned)(want < 1 ? 1 : (want > 2048 ? 2048 : want));
-    hipLaunchKernelGGL(mt_fista_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, theta, grad, x_minus, (long long)n, head, n4, gnorm2, grad_clip,
-                       (int)torch_clip, lr, ak, one_plus_ak);
+    const ArenaSplit s = arena_split({theta, grad, x_minus}, n);
+    hipLaunchKernelGGL(mt_fista_kernel, dim3(s.blocks), dim3(256), 0, (hipStream_t)stream, theta, grad, x_minus, (long long)n, s.head, s.n4, gnorm2,
+                       grad_clip, (int)torch_clip, lr, ak, one_plus_ak);
     FB_CHECK_LAUNCH("fb_mt_fista");
     return FB_OK;
 }

@@ -2,7 +2,7 @@
 // Pure HBM streaming: float4 lanes, grid-stride, FB_MT_BLOCKS blocks; every reduction is two-stage with a fixed
 // order.  Replaces the torch._foreach_* / pow(2).sum() / SGD loops of reference training.py:45-47,162,198-211,
 // modules.py:215-240 and torch.optim.SGD.step.
-#include "common.h"
+#include "arena_update.h"
 
 static inline int mt_blocks(int64_t n) {
     const int64_t b = (n / 4 + 255) / 256;
@@ -253,11 +253,7 @@ extern "C" int fb_mt_norms2(const float* a, const float* b, int64_t n, float* ou
 __global__ __launch_bounds__(256) void mt_clip_sgd_kernel(float* __restrict__ theta, float* __restrict__ grad, float* __restrict__ mom, long long n,
                                                           const float* __restrict__ gnorm2, float grad_clip, float lr, float wd, float mu,
                                                           float damp, int nesterov, int first) {
-    float coef = 1.f;
-    if (grad_clip >= 0.f) {
-        const float norm = sqrtf(gnorm2[0]);
-        if (norm > grad_clip) coef = grad_clip / (norm + 1e-6f);
-    }
+    const float coef = fb_clip_coef(gnorm2, grad_clip, 0);
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
         const float p = theta[i];
         float gr = grad[i];
@@ -301,7 +297,7 @@ extern "C" int fb_mt_scale(float* x, int64_t n, float a, void* stream) {
 __global__ void mt_sam_ascent_kernel(float* __restrict__ theta, const float* __restrict__ grad, float* __restrict__ e_w, long long n,
                                      const float* __restrict__ gnorm2, float grad_clip, float rho) {
     const float norm = sqrtf(gnorm2[0]);
-    const float coef = (grad_clip >= 0.f && norm > grad_clip) ? grad_clip / (norm + 1e-6f) : 1.f;
+    const float coef = fb_clip_coef(gnorm2, grad_clip, 0);
     const float scale = rho / (norm * coef + 1e-12f);
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
         const float e = (grad[i] * coef) * scale;

@@ -16,19 +16,12 @@
 #include <utility>
 #include <vector>
 
-#include "common.h"
+#include "arena_update.h"
 
 namespace {
 
 constexpr int SP_TCO = 64, SP_TCI = 32, SP_PLAIN = 1024, SP_MAX_LAYERS = 512, SP_COLS = 8;
 enum { T_WOFF = 0, T_COUT = 1, T_TAPS = 2, T_CIN = 3, T_CINP = 4, T_WCOFF = 5, T_DGRAD = 6 };
-
-// the torch form of the global clip (torch.nn.utils.clip_grad_norm_): coef = min(1, clip / (norm + 1e-6)); clip < 0: no clip
-__device__ __forceinline__ float torch_clip_coef(const float* __restrict__ gnorm2, float grad_clip) {
-    if (!(grad_clip >= 0.f)) return 1.f;
-    const float c = grad_clip / (sqrtf(gnorm2[0]) + 1e-6f);
-    return c < 1.f ? c : 1.f;
-}
 
 struct SgdHyp { float coef, lr, wd, mu, one_minus_damp; int nesterov, first; };
 
@@ -92,7 +85,7 @@ __global__ __launch_bounds__(256) void mt_sgd_prep_kernel(const SpArgs a) {
     if (bad) return;
     const int total = pre[items];
     SgdHyp h;
-    h.coef = torch_clip_coef(a.gnorm2, a.grad_clip);
+    h.coef = fb_clip_coef(a.gnorm2, a.grad_clip, 1);            // (the mini-batch branch clips with clip_grad_norm_)
     h.lr = a.lr; h.wd = a.wd; h.mu = a.mu; h.one_minus_damp = 1.f - a.damp; h.nesterov = a.nesterov; h.first = a.first;
     const bool use_mom = a.mu != 0.f;
 
@@ -233,7 +226,7 @@ __global__ __launch_bounds__(256) void mt_sgd_torch_kernel(float* __restrict__ t
                                                            long long n, const float* __restrict__ gnorm2, float grad_clip, float lr, float wd,
                                                            float mu, float damp, int nesterov, int first) {
     SgdHyp h;
-    h.coef = torch_clip_coef(gnorm2, grad_clip);
+    h.coef = fb_clip_coef(gnorm2, grad_clip, 1);
     h.lr = lr; h.wd = wd; h.mu = mu; h.one_minus_damp = 1.f - damp; h.nesterov = nesterov; h.first = first;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
         float po, mo;

@@ -8,7 +8,7 @@ Mirrors, for ``hyp.train_stochastic=False``:
   _modify_gradient_params    :187-215   (norm bias, global L2 / L-infinity clip, gradient noise)
   evaluate                   :343-388
   get_loss_fn                :391-413   (cross entropy, label smoothing, incorrect-xent: fused into the head kernel)
-  optim_interface            fullbatch/training/optimizers.py:10-93 (Gradient Descent / line_search none or wolfe, Adam = AdamW, GD-AGC, FISTA; cosine-*, warm-up)
+  optim_interface            fullbatch/training/optimizers.py:10-93 (what it can select: the table in optimizers.py; cosine-*, warm-up)
   _save_to_checkpoint / _load_from_checkpoint   fullbatch/training/utils.py:43-70 (same 5-list layout)
 
 All arithmetic of a step runs in ``libfbengine.so`` on the GPU; torch optimizers/schedulers are instantiated only as
@@ -16,460 +16,39 @@ All arithmetic of a step runs in ``libfbengine.so`` on the GPU; torch optimizers
 exact layout and the LR sequence is produced by the same torch code the reference calls.
 """
 import logging
-import math
 import os
-import re
 import time
 from collections import defaultdict
 
 import numpy as np
 import torch
-from torch.optim.lr_scheduler import _LRScheduler
 
-from . import lib
+from . import lib, optimizers
 from .engine import Engine, stem_patches
+from .optimizers import (FISTA, LARS, SAM, SGD_AGC, WOLFE_DEFAULTS, GradualWarmupScheduler, WolfeGradientDescent, WolfeSearch, _OptimizerWrapper,  # noqa: F401
+                         _scheduler_for, wolfe_constants)     # (the first seven: importers find them here)
 
 log = logging.getLogger("fullbatchtraining_amd")
 
 
-# ----------------------------------------------------------------------------------------------------------------------
-# LR schedule objects (state containers; reference optimizers.py:69-93, additional_optimizers/scheduler.py:32-111)
-# ----------------------------------------------------------------------------------------------------------------------
-class GradualWarmupScheduler(_LRScheduler):
-    """Linear warm-up from 0 (multiplier 1.0) to the base lr over ``total_epoch`` steps, then hands over to
-    ``after_scheduler``.  Attribute names and ``state_dict`` layout follow the reference so checkpoints interchange."""
-
-    def __init__(self, optimizer, multiplier, total_epoch, after_scheduler=None):
-        if multiplier < 1.0:
-            raise ValueError("multiplier should be greater thant or equal to 1.")
-        self.multiplier, self.total_epoch, self.after_scheduler, self.finished = multiplier, total_epoch, after_scheduler, False
-        super().__init__(optimizer)
-
-    def get_lr(self):
-        if self.last_epoch > self.total_epoch:
-            if self.after_scheduler:
-                if not self.finished:
-                    self.after_scheduler.base_lrs = [b * self.multiplier for b in self.base_lrs]
-                    self.finished = True
-                return self.after_scheduler.get_last_lr()
-            return [b * self.multiplier for b in self.base_lrs]
-        if self.multiplier == 1.0:
-            return [b * (float(self.last_epoch) / self.total_epoch) for b in self.base_lrs]
-        return [b * ((self.multiplier - 1.0) * self.last_epoch / self.total_epoch + 1.0) for b in self.base_lrs]
-
-    def step(self, epoch=None):
-        if self.finished and self.after_scheduler:
-            self.after_scheduler.step(None if epoch is None else epoch - self.total_epoch)
-            self._last_lr = self.after_scheduler.get_last_lr()
-        else:
-            return super().step(epoch)
-
-    def state_dict(self):
-        state = {k: v for k, v in self.__dict__.items() if k != "optimizer"}
-        state["after_scheduler"] = {k: v for k, v in self.after_scheduler.__dict__.items() if k != "optimizer"}
-        return state
-
-    def load_state_dict(self, state_dict):
-        after = state_dict.pop("after_scheduler")
-        self.after_scheduler.__dict__.update(after)
-        self.__dict__.update(state_dict)
-
-
 def optim_interface(model, cfg_hyp):
-    """The branches on the hot path: ``Gradient Descent`` + ``line_search: none`` -> torch.optim.SGD, ``line_search: wolfe`` ->
-    ``WolfeGradientDescent``, ``Adam`` -> torch.optim.AdamW, ``GD-AGC`` -> ``SGD_AGC``, ``FISTA`` -> ``FISTA`` (state containers)."""
-    adam, agc, fista = cfg_hyp.optim.name == "Adam", cfg_hyp.optim.name == "GD-AGC", cfg_hyp.optim.name == "FISTA"
-    wolfe = cfg_hyp.optim.name == "Gradient Descent" and cfg_hyp.optim.get("line_search", "none") == "wolfe"
-    if wolfe:                                        # reference optimizers.py:29-30
-        _check_wolfe_scope(cfg_hyp)
-        optimizer = WolfeGradientDescent(model.parameters(), **{k: v for k, v in cfg_hyp.optim.items() if k not in ("name", "line_search")})
-        return optimizer, _scheduler_for(optimizer, cfg_hyp)
-    if cfg_hyp.optim.name == "Gradient Descent" and cfg_hyp.optim.get("line_search", "none") in ("non-monotone", "restarting"):
-        raise NotImplementedError(f"line_search {cfg_hyp.optim.line_search!r}: of the reference's three line searches only the strong-Wolfe search "
-                                  "(line_search=wolfe) runs on the engine; the non-monotone and the restarting search are its follow-ups (both "
-                                  "repeat torch.optim.SGD.step from a saved state, which needs a momentum snapshot next to theta0)")
-    if not adam and not agc and not fista and (cfg_hyp.optim.name != "Gradient Descent" or cfg_hyp.optim.get("line_search", "none") != "none"):
-        raise NotImplementedError(f"optimizer {cfg_hyp.optim.name!r}/{cfg_hyp.optim.get('line_search')!r}: only plain gradient "
-                                  "descent with Nesterov momentum (line_search none or wolfe), AdamW, GD-AGC and FISTA are fused into the engine")
+    """(optimizer, scheduler) as state containers, after the scope check; the descriptor rides along, the scheduler drives the wrapped SGD."""
+    optim = optimizers.select(cfg_hyp)
     mod = cfg_hyp.optim_modification.name
-    if mod not in ("none", "SAM", "LARS", "LARC"):
+    if not optim.search and mod not in ("none", "SAM", "LARS", "LARC"):      # (the search refuses every modification by name)
         raise ValueError(f"Invalid optim_modification {mod} provided.")
-    params = {k: v for k, v in cfg_hyp.optim.items() if k not in ("name", "line_search")}
-    if adam:
-        _check_adam_scope(cfg_hyp)
-        params["betas"] = tuple(params["betas"])
-        optimizer = torch.optim.AdamW(model.parameters(), **params)
-        return optimizer, _scheduler_for(optimizer, cfg_hyp)
-    if agc:                                          # reference optimizers.py:45-52: a group per tensor, no unit clip for groups named linear*
-        _check_agc_scope(cfg_hyp)
-        optimizer = SGD_AGC(model.named_parameters(), **params)
-        for group in optimizer.param_groups:
-            if group["name"].startswith("linear"):
-                group["clipping"] = None
-        return optimizer, _scheduler_for(optimizer, cfg_hyp)
-    if fista:                                        # reference optimizers.py:43-44
-        _check_fista_scope(cfg_hyp)
-        optimizer = FISTA(model.parameters(), **params)
-        return optimizer, _scheduler_for(optimizer, cfg_hyp)
-    if cfg_hyp.only_linear_layers_weight_decay:      # reference optimizers.py:14-21: one param group per tensor, no decay on biases / gains
-        parameter_iterable = []
-        for key, value in model.named_parameters():
-            if len(re.findall("(bias|gain)|skip_gain", key)) > 0:
-                parameter_iterable += [{"params": [value], "weight_decay": 0.0}]
-            else:
-                parameter_iterable += [{"params": [value]}]
-    else:
-        parameter_iterable = model.parameters()
-    optimizer = wrapped = torch.optim.SGD(parameter_iterable, **params)
-    if mod == "SAM":
-        wrapped = SAM(optimizer, rho=cfg_hyp.optim_modification.rho)
-    elif mod in ("LARS", "LARC"):
-        wrapped = LARS(optimizer, trust_coefficient=cfg_hyp.optim_modification.trust_coefficient, clip=mod == "LARC",
-                       eps=cfg_hyp.optim_modification.eps)
-    return wrapped, _scheduler_for(optimizer, cfg_hyp)     # the scheduler drives the wrapped SGD (reference optimizers.py:67 `optimizer.optim`)
-
-
-def _check_adam_scope(cfg_hyp):
-    """What hyp/optim=adam does not cover (the update is ONE fb_mt_adamw launch over the whole arena on one rank)."""
-    if cfg_hyp.optim.get("amsgrad", False):
-        raise NotImplementedError("hyp.optim.amsgrad=True (fb_mt_adamw keeps no running maximum of exp_avg_sq)")
-    if cfg_hyp.optim_modification.name != "none":
-        raise NotImplementedError(f"Adam with optim_modification {cfg_hyp.optim_modification.name!r} (SAM's ascent step and the LARS wrapper are "
-                                  "built around the SGD update)")
-    if cfg_hyp.only_linear_layers_weight_decay:
-        raise NotImplementedError("Adam with only_linear_layers_weight_decay (the AdamW update takes one weight decay for the whole arena)")
-    if torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
-        raise NotImplementedError("Adam on more than one rank (the sharded update would need exp_avg / exp_avg_sq in gather_sharded_state)")
-
-
-def _check_agc_scope(cfg_hyp):
-    """What hyp/optim=gd_agc does not cover (the update is ONE fb_mt_agc_sgd launch over the whole arena on one rank)."""
-    if cfg_hyp.optim_modification.name != "none":
-        raise NotImplementedError(f"GD-AGC with optim_modification {cfg_hyp.optim_modification.name!r} (SAM's ascent step and the LARS wrapper are "
-                                  "built around the plain SGD update)")
-    if cfg_hyp.only_linear_layers_weight_decay:
-        raise NotImplementedError("GD-AGC with only_linear_layers_weight_decay (the reference selects the tensors by a second regex here; the "
-                                  "fb_mt_agc_sgd launch takes one weight decay for the whole arena)")
-    if torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
-        raise NotImplementedError("GD-AGC on more than one rank (the shard boundaries of the sharded update cut through units)")
-
-
-FISTA_KEYS = ("name", "lr", "fista_mod", "projection")
-
-
-def _check_fista_scope(cfg_hyp):
-    """What hyp/optim=fista does not cover (the update is ONE fb_mt_fista launch over the whole arena on one rank).  The name alone does not
-    select it: the reference hands every key of the group to ``FISTA.__init__`` and dies with a TypeError on a foreign one, so a group that was
-    composed for another optimizer and renamed is refused here."""
-    keys = set(cfg_hyp.optim.keys())
-    if keys != set(FISTA_KEYS):
-        foreign, missing = sorted(keys - set(FISTA_KEYS)), sorted(set(FISTA_KEYS) - keys)
-        raise NotImplementedError(f"optimizer 'FISTA' on a group that is not FISTA's (foreign keys {foreign}, missing keys {missing}): select the "
-                                  "optimizer with hyp/optim=fista")
-    if cfg_hyp.optim.projection is not None:
-        raise NotImplementedError(f"FISTA with projection {cfg_hyp.optim.projection!r} (the reference takes a function handle, which no preset "
-                                  "can carry; fb_mt_fista applies none)")
-    if cfg_hyp.optim_modification.name != "none":
-        raise NotImplementedError(f"FISTA with optim_modification {cfg_hyp.optim_modification.name!r} (SAM's ascent step and the LARS wrapper are "
-                                  "built around the SGD update)")
-    if cfg_hyp.only_linear_layers_weight_decay:
-        raise NotImplementedError("FISTA with only_linear_layers_weight_decay (FISTA has no weight decay; the fb_mt_fista launch takes one group "
-                                  "for the whole arena)")
-    if torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
-        raise NotImplementedError("FISTA on more than one rank (the sharded update would need x_minus in gather_sharded_state)")
-    _fista_mod(cfg_hyp.optim.fista_mod)
-
-
-def _fista_mod(fista_mod):
-    """``fista_mod`` as a tuple of three floats; ValueError for anything but three finite numbers."""
-    try:
-        mod = tuple(float(v) for v in fista_mod)
-    except (TypeError, ValueError):
-        mod = ()
-    if len(mod) != 3 or not all(math.isfinite(v) for v in mod) or any(isinstance(v, (bool, str)) for v in fista_mod):
-        raise ValueError(f"hyp.optim.fista_mod must be three finite numbers (p, q, r), got {fista_mod!r}")
-    return mod
-
-
-class FISTA(torch.optim.Optimizer):
-    """State container with the layout of the reference's ``FISTA`` (additional_optimizers/fista.py): one param group with ``lr``,
-    ``fista_mod``, ``projection``; ``state[p] = {"x+", "x-", "tk"}``.  It holds no arithmetic: the update is the engine's fb_mt_fista on the
-    arena."""
-
-    def __init__(self, params, projection=None, lr=1e-4, fista_mod=(1.0, 1.0, 4.0)):
-        if not 0.0 <= lr:
-            raise ValueError(f"Invalid learning rate: {lr}")
-        super().__init__(params, dict(lr=lr, fista_mod=fista_mod, projection=projection))
-
-    def step(self, closure=None):
-        raise RuntimeError("FISTA is a state container: the update runs in the engine (Engine.fista_step)")
-
-
-WOLFE_DEFAULTS = dict(c1=1e-4, c2=0.9, alpha_max=10.0, max_iter=10)      # WolfeGradientDescent.__init__ (the reference's gd.yaml carries none of them)
-
-
-def wolfe_constants(cfg_optim):
-    """(c1, c2, alpha_max, max_iter) of a ``Gradient Descent`` group: the group's own values where it has them (``+hyp.optim.c1=...``), the
-    reference constructor's defaults otherwise."""
-    return tuple(cfg_optim.get(k, v) for k, v in WOLFE_DEFAULTS.items())
-
-
-def _check_wolfe_scope(cfg_hyp):
-    """What hyp.optim.line_search=wolfe does not cover (the search runs on the whole arena of one rank, around the full-batch closure)."""
-    if cfg_hyp.train_stochastic:
-        raise NotImplementedError("line_search=wolfe with hyp.train_stochastic (the reference calls optimizer.step() without a closure in the "
-                                  "mini-batch branch, training.py:274, and dies in WolfeGradientDescent.step)")
-    if cfg_hyp.optim_modification.name != "none":
-        raise NotImplementedError(f"line_search=wolfe with optim_modification {cfg_hyp.optim_modification.name!r} (SAM's two closures and the LARS "
-                                  "wrapper are built around one SGD update per step, not around a search that evaluates the closure itself)")
-    if cfg_hyp.only_linear_layers_weight_decay:
-        raise NotImplementedError("line_search=wolfe with only_linear_layers_weight_decay (fb_mt_wolfe_direction and fb_mt_wolfe_phi_grad take one "
-                                  "weight decay for the whole arena)")
-    if torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
-        raise NotImplementedError("line_search=wolfe on more than one rank (every evaluation would need the exchanged gradient whole on every rank "
-                                  "and one agreed phi'; the sharded update has neither)")
-
-
-class WolfeGradientDescent(torch.optim.Optimizer):
-    """State container with the layout of the reference's ``WolfeGradientDescent`` (additional_optimizers/sgd_linesearch.py:183-203): one param
-    group with the SGD keys and ``c1``, ``c2``, ``alpha_max``, ``max_iter``; ``state[p]["momentum_buffer"]`` and the bare key ``state["alpha"]``
-    (the step length the last search returned).  It holds no arithmetic: direction, trial points and phi' are the engine's fb_mt_wolfe_* on the
-    arena, the search is ``WolfeSearch``."""
-
-    def __init__(self, params, lr=0.1, momentum=0, dampening=0, weight_decay=0, nesterov=False, c1=1e-4, c2=0.9, alpha_max=10.0, max_iter=10):
-        if lr < 0.0:
-            raise ValueError("Invalid learning rate: {}".format(lr))
-        if momentum < 0.0:
-            raise ValueError("Invalid momentum value: {}".format(momentum))
-        if weight_decay < 0.0:
-            raise ValueError("Invalid weight_decay value: {}".format(weight_decay))
-        if nesterov and (momentum <= 0 or dampening != 0):
-            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
-        super().__init__(params, dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov, c1=c1, c2=c2,
-                                      alpha_max=alpha_max, max_iter=max_iter))
-
-    def step(self, closure=None):
-        raise RuntimeError("WolfeGradientDescent is a state container: the step runs in FullBatchTrainer.step (WolfeSearch on the engine)")
-
-
-class WolfeSearch:
-    """The control flow of ``WolfeGradientDescent.step`` / ``_zoom`` / ``_interpolate`` (sgd_linesearch.py:303-381) on Python floats: the
-    reference's expressions in the reference's order, its look-up table (a ``defaultdict(dict)`` keyed by alpha, so an alpha that was seen is not
-    evaluated again), its exits -- and its quirks: ``prev_loss`` is never updated, a zoom that runs out of rounds returns an alpha it never
-    evaluated, ``math.sqrt`` of a negative discriminant raises ValueError.  It sees the problem only through ``evaluate(alpha) -> (loss,
-    phi_grad)``: the parameters are left wherever the last evaluation put them.
-
-    After ``search``: ``evaluated`` (every alpha handed to ``evaluate``, in order), ``trace`` (every inequality decided, as
-    ``(name, alpha, left, right)``), ``exit`` (which way the outer loop ended), ``zoom_exit`` (which way the zoom ended, if there was one) and
-    ``table_hits`` (how often the table spared an evaluation)."""
-
-    def __init__(self, c1=1e-4, c2=0.9, alpha_max=10.0, max_iter=10):
-        self.c1, self.c2, self.alpha_max, self.max_iter = c1, c2, alpha_max, max_iter
-        self.evaluated, self.trace, self.exit, self.zoom_exit, self.table_hits = [], [], None, None, 0
-
-    def _evaluate_phi(self, alpha, evaluate, phi):
-        if alpha not in phi:
-            loss, phi_grad = evaluate(alpha)
-            self.evaluated.append(alpha)
-            phi[alpha] = dict(val=loss, grad=phi_grad)
-        else:
-            self.table_hits += 1
-
-    def search(self, loss0, phi_grad0, evaluate):
-        """``loss0 = phi(0)``, ``phi_grad0 = phi'(0)`` -> the alpha the reference stores in ``state['alpha']``."""
-        self.evaluated, self.trace, self.exit, self.zoom_exit, self.table_hits = [], [], "max_iter", None, 0
-        alpha = 1.0
-        phi = defaultdict(dict)
-        phi[0] = dict(val=loss0, grad=phi_grad0)
-        prev_loss = float("inf")
-        prev_alpha = 0
-        for iteration in range(self.max_iter):
-            self._evaluate_phi(alpha, evaluate, phi)
-            sufficient_loss = phi[0]["val"] + self.c1 * alpha * phi[0]["grad"]
-            self.trace.append(("decrease", alpha, phi[alpha]["val"], sufficient_loss))
-            if (phi[alpha]["val"] > sufficient_loss) or (phi[alpha]["val"] > prev_loss):
-                alpha = self._zoom(prev_alpha, alpha, evaluate, phi)
-                self.exit = "zoom-1"
-                break
-            self.trace.append(("curvature", alpha, abs(phi[alpha]["grad"]), -self.c2 * phi[0]["grad"]))
-            if abs(phi[alpha]["grad"]) <= -self.c2 * phi[0]["grad"]:
-                self.exit = "accepted"
-                break
-            self.trace.append(("sign", alpha, phi[alpha]["grad"], 0.0))
-            if phi[alpha]["grad"] >= 0:
-                alpha = self._zoom(alpha, prev_alpha, evaluate, phi)
-                self.exit = "zoom-2"
-                break
-            prev_alpha = alpha
-            alpha = min(alpha * 2.5, self.alpha_max)
-            if alpha == self.alpha_max:
-                self.exit = "alpha_max"
-                break
-        return alpha
-
-    def _zoom(self, alpha_low, alpha_high, evaluate, phi):
-        for iteration in range(self.max_iter):
-            if abs(alpha_low - alpha_high) < 1e-4:
-                self.zoom_exit = "interval"
-                return alpha_low
-            alpha = self._interpolate(alpha_low, alpha_high, phi)
-            self._evaluate_phi(alpha, evaluate, phi)
-            sufficient_loss = phi[0]["val"] + self.c1 * alpha * phi[0]["grad"]
-            self.trace.append(("zoom-decrease", alpha, phi[alpha]["val"], sufficient_loss))
-            self.trace.append(("zoom-low", alpha, phi[alpha]["val"], phi[alpha_low]["val"]))
-            if (phi[alpha]["val"] > sufficient_loss) or (phi[alpha]["val"] > phi[alpha_low]["val"]):
-                alpha_high = alpha
-            else:
-                self.trace.append(("zoom-curvature", alpha, phi[alpha]["grad"], -self.c2 * phi[0]["grad"]))
-                if (phi[alpha]["grad"]) <= -self.c2 * phi[0]["grad"]:
-                    self.zoom_exit = "curvature"
-                    return alpha
-                self.trace.append(("zoom-sign", alpha, phi[alpha]["grad"] * (alpha_high - alpha_low), 0.0))
-                if phi[alpha]["grad"] * (alpha_high - alpha_low) >= 0:
-                    alpha_high = alpha_low
-                alpha_low = alpha
-        self.zoom_exit = "exhausted"
-        return self._interpolate(alpha_low, alpha_high, phi)
-
-    @staticmethod
-    def _interpolate(alpha1, alpha2, phi):
-        """Cubic interpolation as in Nocedal and Wright."""
-        if alpha1 == alpha2:
-            return alpha1
-        quotient = (phi[alpha1]["val"] - phi[alpha2]["val"]) / (alpha1 - alpha2)
-        d_1 = phi[alpha1]["grad"] + phi[alpha2]["grad"] - 3 * quotient
-        d_2 = math.copysign(1.0, alpha2 - alpha1) * math.sqrt(d_1**2 - phi[alpha1]["grad"] * phi[alpha2]["grad"])
-        update_nom = phi[alpha2]["grad"] + d_2 - d_1
-        update_denom = phi[alpha2]["grad"] - phi[alpha1]["grad"] + 2 * d_2
-        return alpha2 - (alpha2 - alpha1) * update_nom / update_denom
-
-
-class SGD_AGC(torch.optim.Optimizer):
-    """State container with the layout of the reference's ``SGD_AGC`` (additional_optimizers/sgd_agc.py): one param group per named tensor
-    carrying ``name``, ``clipping``, ``eps`` and the SGD keys; ``state[p]["momentum_buffer"]``.  It holds no arithmetic: the update is the
-    engine's fb_mt_agc_sgd on the arena."""
-
-    def __init__(self, named_params, lr, momentum=0, dampening=0, weight_decay=0, nesterov=False, clipping=None, eps=1e-3):
-        if lr < 0.0 or momentum < 0.0 or weight_decay < 0.0:
-            raise ValueError(f"Invalid lr / momentum / weight_decay: {lr} / {momentum} / {weight_decay}")
-        if nesterov and (momentum <= 0 or dampening != 0):
-            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
-        defaults = dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov, clipping=clipping, eps=eps)
-        super().__init__([{"params": param, "name": name} for name, param in named_params], defaults)
-
-    def step(self, closure=None):
-        raise RuntimeError("SGD_AGC is a state container: the update runs in the engine (Engine.agc_sgd_step)")
-
-
-def _scheduler_for(optimizer, cfg_hyp):
-    """The lr schedule of reference optimizers.py:69-91 around the (unwrapped) optimizer."""
-    sched = cfg_hyp.scheduler
-    if sched == "cosine-decay-floored":
-        scheduler = torch.optim.lr_scheduler.CosineAnnealingLR(optimizer, cfg_hyp.steps, eta_min=cfg_hyp.optim.lr / 25)
-    elif sched == "cosine-decay":
-        scheduler = torch.optim.lr_scheduler.CosineAnnealingLR(optimizer, cfg_hyp.steps, eta_min=0.0)
-    elif sched == "cosine-4000":
-        scheduler = torch.optim.lr_scheduler.CosineAnnealingLR(optimizer, 4000, eta_min=0.0)
-    elif sched == "linear":
-        scheduler = torch.optim.lr_scheduler.MultiStepLR(
-            optimizer, milestones=[cfg_hyp.steps // 2.667, cfg_hyp.steps // 1.6, cfg_hyp.steps // 1.142], gamma=0.1)
-    elif sched == "exponential":
-        scheduler = torch.optim.lr_scheduler.ExponentialLR(optimizer, gamma=0.99)
-    elif sched in ["", " ", None]:
-        scheduler = torch.optim.lr_scheduler.MultiStepLR(optimizer, milestones=[], gamma=1)
-    else:
-        raise ValueError(f"Invalid scheduler {sched} provided.")
-    if cfg_hyp.warmup > 0:
-        scheduler = GradualWarmupScheduler(optimizer, multiplier=1.0, total_epoch=cfg_hyp.warmup, after_scheduler=scheduler)
-    # The torch optimizer is a STATE CONTAINER here (param_groups / momentum buffers in the checkpoint layout): the update itself is the engine's
-    # fb_mt_clip_sgd / fb_mt_adamw / fb_mt_agc_sgd / fb_mt_fista on the arena, so ``optimizer.step()`` is never called -- tell the schedulers that updates do happen, or the
-    # first ``scheduler.step()`` warns "lr_scheduler.step() before optimizer.step()" on every run
-    optimizer._opt_called = True
-    return scheduler
-
-
-class _OptimizerWrapper:
-    """State container with the reference wrappers' surface (``.optim``, shared ``param_groups``, attribute pass-through, pickling
-    via the wrapped optimizer; reference additional_optimizers/sam.py:34-54, lars.py:41-59).  The arithmetic runs in the engine."""
-
-    def __init__(self, optimizer):
-        self.optim = optimizer
-
-    @property
-    def param_groups(self):
-        """Always the wrapped optimizer's CURRENT list: ``Optimizer.load_state_dict`` replaces it, and the scheduler (which drives the
-        wrapped SGD) writes the lr there -- a reference held from construction would freeze the lr of a resumed SAM / LARS run."""
-        return self.optim.param_groups
-
-    @param_groups.setter
-    def param_groups(self, value):
-        self.optim.param_groups = value
-
-    def __getstate__(self):
-        return self.optim.__getstate__()
-
-    def __setstate__(self, state):
-        self.optim.__setstate__(state)
-
-    def __repr__(self):
-        return self.optim.__repr__()
-
-    def __getattr__(self, name):
-        if name == "optim":
-            raise AttributeError(name)
-        return getattr(self.optim, name)
-
-
-class SAM(_OptimizerWrapper):
-    """Sharpness-aware minimisation (reference additional_optimizers/sam.py): the step evaluates the full-batch closure twice --
-    ``FullBatchTrainer.step`` runs closure -> ``Engine.sam_ascent`` -> closure -> ``Engine.sam_restore`` -> SGD update."""
-
-    def __init__(self, optimizer, rho=0.05):
-        assert rho >= 0.0, f"Invalid rho, should be non-negative: {rho}"
-        super().__init__(optimizer)
-        self.rho = rho
-
-
-class LARS(_OptimizerWrapper):
-    """LARS / LARC wrapper (reference additional_optimizers/lars.py).  Around a closure the reference's wrapper has exactly one
-    effect: it rescales ``p.grad`` of the PREVIOUS step, zeroes the group weight decay and then calls ``SGD.step(closure)``, whose
-    closure assigns fresh gradients (training.py:183-184) -- the update is plain SGD without weight decay, independent of
-    ``trust_coefficient`` / ``clip`` / ``eps`` (pinned against the reference in tests/golden/scenarios_n4.npz)."""
-
-    def __init__(self, optimizer, trust_coefficient=0.02, clip=False, eps=1e-8):
-        super().__init__(optimizer)
-        self.trust_coefficient, self.clip, self.eps = trust_coefficient, clip, eps
+    optim.check(cfg_hyp)
+    optimizer = optim.container(model, cfg_hyp)
+    optimizer.descriptor = optim
+    return optimizer, _scheduler_for(optimizer.optim if isinstance(optimizer, _OptimizerWrapper) else optimizer, cfg_hyp)
 
 
 # ----------------------------------------------------------------------------------------------------------------------
 # checkpoints (reference training/utils.py:43-70)
 # ----------------------------------------------------------------------------------------------------------------------
 def _sync_optimizer_state(engine, model, optimizer):
-    """Expose the arena's momentum as torch SGD state (AdamW: step / exp_avg / exp_avg_sq; FISTA: x+ / x- / tk) so ``optimizer.state_dict()`` has the reference
-    layout."""
-    if isinstance(optimizer, torch.optim.AdamW):
-        if getattr(engine, "adam_step", 0) == 0:
-            return
-        exp_avg, exp_avg_sq, step = engine.adam_state()
-        for p, m, v in zip(model.parameters(), exp_avg, exp_avg_sq):     # torch's own state: a float32 scalar step, buffers shaped like p
-            optimizer.state[p] = {"step": torch.tensor(float(step), dtype=torch.float32), "exp_avg": m.to(p.device, p.dtype),
-                                  "exp_avg_sq": v.to(p.device, p.dtype)}
-        return
-    if isinstance(optimizer, FISTA):
-        if getattr(engine, "x_minus", None) is None:
-            return
-        x_minus, tk = engine.fista_state()
-        for p, x in zip(model.parameters(), x_minus):   # the reference's own state: after a step x+ holds the values of x-; tk a float32 tensor [1]
-            x = x.to(p.device, p.dtype)
-            optimizer.state[p] = {"x+": x.clone(), "x-": x, "tk": torch.full((1,), float(tk), dtype=torch.float32, device=p.device)}
-        return
-    if engine.first_step:
-        return
-    for p, buf in zip(model.parameters(), engine.momentum_state()):
-        optimizer.state[p]["momentum_buffer"] = buf.to(p.device, p.dtype)
-    if getattr(engine, "e_w", None) is not None:       # SAM keeps its last ascent step in the wrapped optimizer's state (sam.py:66)
-        for p, e in zip(model.parameters(), engine.sam_state()):
-            optimizer.state[p]["e_w"] = e.to(p.device, p.dtype)
+    """Expose the engine's state as ``optimizer.state`` in the reference layout (a container ``optim_interface`` did not build: SGD's momentum)."""
+    getattr(optimizer, "descriptor", optimizers.TABLE["Gradient Descent", "none"]).sync(engine, model, optimizer)
 
 
 def _save_to_checkpoint(model, optimizer, scheduler, scaler, counter, file="checkpoints/fb.pth", engine=None):
@@ -493,14 +72,7 @@ def _load_from_checkpoint(model, optimizer, scheduler, scaler, counter, max_step
     counter.step = step
     if engine is not None:
         engine.load_from_model(model)
-        states = [optimizer.state[p] for p in model.parameters() if p in optimizer.state]
-        if isinstance(optimizer, torch.optim.AdamW) and len(states) == len(list(model.parameters())) and all("exp_avg" in st for st in states):
-            engine.load_adam_state([st["exp_avg"] for st in states], [st["exp_avg_sq"] for st in states], int(float(states[0]["step"])))
-        if isinstance(optimizer, FISTA) and len(states) == len(list(model.parameters())) and all("x-" in st for st in states):
-            engine.load_fista_state([st["x-"] for st in states], np.float32(states[0]["tk"].detach().cpu().numpy().reshape(-1)[0]))
-        bufs = [optimizer.state[p].get("momentum_buffer") for p in model.parameters() if p in optimizer.state]
-        if len(bufs) == len(list(model.parameters())) and all(b is not None for b in bufs):
-            engine.load_momentum(bufs)
+        getattr(optimizer, "descriptor", optimizers.TABLE["Gradient Descent", "none"]).load(engine, model, optimizer)
     if step >= max_steps:
         raise ValueError("Maximum step size reached. Terminating computations.")
     print(f"Existing checkpoint loaded successfully. Continuing to train from step {step}.")
@@ -588,14 +160,9 @@ def _check_scope(cfg, branch="full-batch"):
     if bool(hyp.train_stochastic) != (branch == "stochastic"):
         raise NotImplementedError(f"hyp.train_stochastic={bool(hyp.train_stochastic)} does not select the {branch} branch this check was asked about "
                                   "(FullBatchTrainer runs both: it checks the branch the configuration selects)")
-    if hyp.optim.name == "Adam":
-        _check_adam_scope(hyp)
-    if hyp.optim.name == "GD-AGC":
-        _check_agc_scope(hyp)
-    if hyp.optim.name == "FISTA":
-        _check_fista_scope(hyp)
-    if hyp.optim.name == "Gradient Descent" and hyp.optim.get("line_search", "none") == "wolfe":
-        _check_wolfe_scope(hyp)
+    optim = optimizers.select(hyp, refuse=False)    # (what the table does not have is optim_interface's to refuse, after everything here)
+    if optim is not None:
+        optim.check(hyp)
     if hyp.train_stochastic:         # mini-batch SGD mode (reference training.py:241-286)
         if torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
             raise NotImplementedError("hyp.train_stochastic on more than one rank (the reference all-reduces every mini-batch gradient; the engine's "
@@ -730,22 +297,14 @@ class FullBatchTrainer:
         self.cfg, self.model = cfg, model
         self.device = torch.device(setup["device"]) if not isinstance(setup["device"], torch.device) else setup["device"]
         self.optimizer, self.scheduler = optim_interface(model, cfg.hyp)
-        # (the engine applies the update on its arena, fb_mt_clip_sgd; the torch optimizer is the state container the checkpoint layout wants)
+        self.optim = self.optimizer.descriptor   # (its update runs on the engine's arena; the torch optimizer is the state container the checkpoint layout wants)
         self.loss_fn = get_loss_fn(cfg.hyp, cfg.data.batch_size)
         self.world = torch.distributed.get_world_size() if torch.distributed.is_initialized() else 1
         self.rank = torch.distributed.get_rank() if torch.distributed.is_initialized() else 0
         # the multi-process code path (collectives, sharded update); FB_FORCE_DIST=1 takes it with an initialised process group of ONE
         # rank as well, which runs the real RCCL reduce-scatter / all-gather calls on a 1-GPU box (tests/test_gpu_sharded.py)
         self.multi = self.world > 1 or (torch.distributed.is_initialized() and os.environ.get("FB_FORCE_DIST") == "1")
-        if self.multi and cfg.hyp.optim.name == "Adam":
-            raise NotImplementedError("Adam on the multi-process code path (the sharded update would need exp_avg / exp_avg_sq in gather_sharded_state)")
-        if self.multi and cfg.hyp.optim.name == "GD-AGC":
-            raise NotImplementedError("GD-AGC on the multi-process code path (the shard boundaries of the sharded update cut through units)")
-        if self.multi and cfg.hyp.optim.name == "FISTA":
-            raise NotImplementedError("FISTA on the multi-process code path (the sharded update would need x_minus in gather_sharded_state)")
-        if self.multi and cfg.hyp.optim.name == "Gradient Descent" and cfg.hyp.optim.get("line_search", "none") == "wolfe":
-            raise NotImplementedError("line_search=wolfe on the multi-process code path (every evaluation would need the exchanged gradient whole "
-                                      "on every rank and one agreed phi'; the sharded update has neither)")
+        self.optim.check(cfg.hyp, multi=self.multi)
         # a shuffling train loader: the dataset stays resident in dataset order and every step regathers it in the order of a new
         # pass over the loader's batch sampler (reference: `for block, (inputs, labels) in enumerate(trainloader)` every step)
         self.shuffler = trainloader if _is_shuffling(trainloader) else None
@@ -908,8 +467,6 @@ class FullBatchTrainer:
                                                     weight_decay=0.0 if mod in ("LARS", "LARC") else None, exchange=exchange)
             self._state_is_sharded = True        # momentum / clipped gradient complete only on each rank's shard until gather_state()
         else:
-            o = hyp.optim
-
             def modify():
                 """``_modify_gradient_params`` up to the clip coefficient (reference training.py:187-204): norm bias on the averaged
                 gradient, then the clip norm (L2 or L-infinity) into ``eng.norms2[0]``; ``eng.norms2[1]`` = |theta|^2."""
@@ -937,7 +494,7 @@ class FullBatchTrainer:
                 return norms
 
             clip = None if noisy else hyp.grad_clip          # (already applied in place where noise follows it)
-            if o.name == "Gradient Descent" and o.get("line_search", "none") == "wolfe":
+            if self.optim.search:
                 self._wolfe_step(closure, modify, clip, lr, train_time, (loss_k, correct_k, sq_k))
                 self.scheduler.step()
                 return
@@ -951,11 +508,11 @@ class FullBatchTrainer:
                 norms = modify()                 # param_norm of the second record is taken at theta + e_w, like the reference's
                 self._record_stats(loss_k, correct_k, sq_k, norms, lr, train_time)
                 eng.sam_restore()
-                self._update(lr, grad_clip=clip)
+                self.optim.update(eng, hyp, lr, clip, optimizer=self.optimizer)
                 self.scheduler.step()
                 return
             # LARS / LARC: the wrapper zeroes the weight decay around SGD.step(closure) and nothing else survives the closure (see LARS)
-            self._update(lr, zero_wd=mod in ("LARS", "LARC"), grad_clip=clip)
+            self.optim.update(eng, hyp, lr, clip, zero_wd=mod in ("LARS", "LARC"), optimizer=self.optimizer)
             self._record_stats(loss_k, correct_k, sq_k, norms, lr, train_time)
             self.scheduler.step()
             return
@@ -996,7 +553,7 @@ class FullBatchTrainer:
         the SGD update; ``_modify_gradient_params`` is commented out there, so there is no norm bias, no gradient noise and no
         preclip_gradnorm / clipped_step.  Nothing here waits for the device: losses, hits and norms of the blocks land in device arrays that
         ``_record_stats`` reads back once."""
-        eng, hyp, o, gr = self.engine, self.cfg.hyp, self.cfg.hyp.optim, self.cfg.hyp.grad_reg
+        eng, hyp, gr = self.engine, self.cfg.hyp, self.cfg.hyp.grad_reg
         nb, cp = self.num_blocks, self.chunk_pad
         f32 = dict(device=self.device, dtype=torch.float32)
         loss_all, correct_all, sq_all = torch.empty(nb, **f32), torch.empty(nb, **f32), torch.empty(nb, **f32)
@@ -1017,19 +574,10 @@ class FullBatchTrainer:
             # ---- the update section: norm, update, compute-dtype copies of the new parameters
             if hyp.grad_clip is not None:        # |avg|^2 of the (regularised) block gradient for the clip
                 lib.call("fb_mt_norms2", eng.avg.data_ptr(), None, eng.plan.P, eng.norms2.data_ptr(), eng.mt_ws.data_ptr())
-            if o.name == "Adam":                 # torch.optim.AdamW after clip_grad_norm_, then the unfused weight copies
-                eng.adamw_step(lr, o.weight_decay, o.betas, o.eps, hyp.grad_clip, torch_clip=True)
+            fused = self.sgd_fused and self.optim.launch is None   # (only plain SGD's update can write the weight copies in the same launch)
+            self.optim.update(eng, hyp, lr, hyp.grad_clip, torch_clip=True, fused=fused)
+            if not fused:                        # the composition: fb_weight_prep per layer (a recorded list)
                 eng.prep_weights(eng.theta, 1)
-            elif o.name == "GD-AGC":             # SGD_AGC after clip_grad_norm_, then the unfused weight copies
-                eng.agc_sgd_step(lr, o.weight_decay, o.momentum, o.dampening, o.nesterov, o.clipping, o.eps, hyp.grad_clip, torch_clip=True)
-                eng.prep_weights(eng.theta, 1)
-            elif o.name == "FISTA":              # FISTA after clip_grad_norm_, then the unfused weight copies
-                eng.fista_step(lr, o.fista_mod, hyp.grad_clip, torch_clip=True)
-                eng.prep_weights(eng.theta, 1)
-            else:
-                eng.sgd_prep_step(lr, o.weight_decay, o.momentum, o.dampening, o.nesterov, hyp.grad_clip, fused=self.sgd_fused)
-                if not self.sgd_fused:           # the composition: fb_weight_prep per layer (a recorded list)
-                    eng.prep_weights(eng.theta, 1)
             if sections is not None:
                 end = torch.cuda.Event(enable_timing=True)
                 end.record()
@@ -1065,22 +613,6 @@ class FullBatchTrainer:
             from .parallel import gather_sharded_state
             gather_sharded_state(self)
             self._state_is_sharded = False
-
-    def _update(self, lr, zero_wd=False, grad_clip=None):
-        """Clip + Nesterov SGD on the arena; per-tensor weight decay when the optimizer has one param group per tensor
-        (``hyp.only_linear_layers_weight_decay``, reference optimizers.py:14-21)."""
-        eng, hyp, o = self.engine, self.cfg.hyp, self.cfg.hyp.optim
-        if o.name == "Adam":                     # one fb_mt_adamw launch; the clip is this branch's form and clips eng.avg in place
-            eng.adamw_step(lr, o.weight_decay, o.betas, o.eps, grad_clip)
-        elif o.name == "GD-AGC":                 # one fb_mt_agc_sgd launch; eng.avg keeps the global clip only
-            eng.agc_sgd_step(lr, o.weight_decay, o.momentum, o.dampening, o.nesterov, o.clipping, o.eps, grad_clip)
-        elif o.name == "FISTA":                  # one fb_mt_fista launch; the clip is this branch's form and clips eng.avg in place
-            eng.fista_step(lr, o.fista_mod, grad_clip)
-        elif hyp.only_linear_layers_weight_decay and not zero_wd:
-            wds = [g["weight_decay"] for g in self.optimizer.param_groups]
-            eng.sgd_step_per_tensor(lr, wds, o.momentum, o.dampening, o.nesterov, grad_clip)
-        else:
-            eng.sgd_step(lr, 0.0 if zero_wd else o.weight_decay, o.momentum, o.dampening, o.nesterov, grad_clip)
 
     def _regather_shuffled(self):
         """A new pass over the shuffling train loader: its batch sampler gives this step's sample order (rank 0's draw on several
